@@ -14,6 +14,13 @@ N > 1 (launched through torch.distributed.run, one rank per GPU): the SAME 256^3
 (2 -> 2x1x1, 4 -> 2x2x1, 8 -> 2x2x2 boxes), the subdomains in it and the separators they list first;
 halo values and the V-sum hand-off travel through torch.distributed (RCCL) -- DESIGN.md section
 "multi-GPU".  value = global DoF / time.  `--replicas` runs N independent copies instead.
+
+A plain run does only what the headline figure needs: set up (Initialize + one Compute), warm up, time the K steps, write the
+outputs if `--dump-outputs DIR` is given, print the line.  `--full` adds the other measurements and checks: a second Compute
+with the pattern reused (`config.recompute_s`, `setup_roofline`), the device GMRES solve (`krylov`) and, on one GPU, the CPU
+baseline (`cpu_baseline`).  `--dump-outputs DIR` writes what the last timed ApplyInverse returned (x) as float64 .npy files,
+a fixed seeded sample of its entries where it is larger than 32 MiB; the inputs are the same in every run with the same
+arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -97,6 +104,24 @@ def cpu_baseline(problem, re, n, sx, levels, seconds_budget=30.0, gpu_lib_ok=Tru
 
 PROBLEM = {"stokes": "Stokes", "darcy": "Darcy", "cavity": "Cavity"}
 
+DUMP_ENTRIES = 1 << 22   # 32 MiB of float64 over all ranks and columns: the cap of --dump-outputs
+
+
+def dump_outputs(out_dir, x, rank, world):
+    """--dump-outputs: x (rows this rank owns; one row per right-hand side with --nvec > 1) as float64 .npy.  Above the cap
+    the same seeded positions of every right-hand side are kept, sorted (x_sample.npy); they depend on the arguments only."""
+    os.makedirs(out_dir, exist_ok=True)
+    nvec = x.shape[0] if x.ndim > 1 else 1
+    n = x.shape[-1]
+    keep = DUMP_ENTRIES // (nvec * world)
+    name = "x" if world == 1 else "x_rank%d" % rank
+    if n > keep:
+        idx = np.unique(np.random.default_rng(20240601 + rank).integers(0, n, size=keep))
+        x = x[..., torch.from_numpy(idx).to(x.device)] if torch.is_tensor(x) else x[..., idx]
+        name += "_sample"
+    x = x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(x, dtype=np.float64))
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -114,9 +139,15 @@ def main():
                     help="right-hand sides per ApplyInverse (Epetra_MultiVector columns); > 1: the factors are streamed once per "
                          "group of 4 columns, value = DoF x vectors / s")
     ap.add_argument("--replicas", action="store_true", help="N > 1: independent copies instead of the sharded problem")
-    ap.add_argument("--krylov", dest="krylov", action="store_true", default=True,
-                    help="(default) after the timed region: solve K x = b (b = K x_ex) with right-preconditioned GMRES on the "
-                         "device (hymls_amd.Solver, relative residual 1e-8) and report the iteration count and time")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the numeric recompute (recompute_s, setup_roofline), "
+                         "the device GMRES solve (krylov) and, on one GPU, the CPU baseline (cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write what the last one returned (x) to DIR/*.npy, float64; above 32 MiB a "
+                         "fixed seeded sample of its entries")
+    ap.add_argument("--krylov", dest="krylov", action="store_true", default=None,
+                    help="(default with --full) after the timed region: solve K x = b (b = K x_ex) with right-preconditioned "
+                         "GMRES on the device (hymls_amd.Solver, relative residual 1e-8) and report the iteration count and time")
     ap.add_argument("--no-krylov", dest="krylov", action="store_false")
     ap.add_argument("--krylov-restart", type=int, default=100, help="GMRES restart length ('Num Blocks')")
     ap.add_argument("--share-gpu", action="store_true",
@@ -126,7 +157,7 @@ def main():
                     help="N = 1: take the sharded code path anyway (one rank exchanging with itself over the transport): "
                          "measures what packing + callbacks + collectives cost per ApplyInverse")
     ap.add_argument("--cpu-n", type=int, default=48, help="grid size of the CPU baseline's bounded sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL)")
     ap.add_argument("--transport", choices=["rccl", "torch"], default="rccl",
                     help="sharded runs: 'rccl' = the library's built-in transport (ncclSend/ncclRecv groups on its stream, "
@@ -135,6 +166,8 @@ def main():
                     help="TEST ONLY: drive the host-logic simulator on the CPU (tests/test_bench_multirank.py); "
                          "numbers produced this way are meaningless and are marked as such")
     args = ap.parse_args()
+    if args.krylov is None:
+        args.krylov = args.full
     # exactly ONE line on stdout: libraries (RCCL prints its version banner there) write to stderr from here on
     sys.stdout.flush()
     json_fd = os.dup(1)
@@ -224,7 +257,9 @@ def main():
         del rows
         P.Initialize(); t_init = time.time() - t0
         t0 = time.time(); P.Compute(); t_comp = time.time() - t0
-        t0 = time.time(); P.Compute(); t_recomp = time.time() - t0     # SetMatrix-style recompute: symbolic work reused
+        t_recomp = None
+        if args.full:
+            t0 = time.time(); P.Compute(); t_recomp = time.time() - t0     # SetMatrix-style recompute: symbolic work reused
         N_local = P.OwnedRows().size
         N_global = nx * ny * nz * 4
     else:
@@ -236,7 +271,9 @@ def main():
         P = hymls_amd.Preconditioner((rp, ci, va), prm, testVector=tv, device=local_rank, lib=lib)
         t0 = time.time(); P.Initialize(); t_init = time.time() - t0
         t0 = time.time(); P.Compute(); t_comp = time.time() - t0
-        t0 = time.time(); P.Compute(); t_recomp = time.time() - t0     # SetMatrix-style recompute: symbolic work reused
+        t_recomp = None
+        if args.full:
+            t0 = time.time(); P.Compute(); t_recomp = time.time() - t0     # SetMatrix-style recompute: symbolic work reused
         N_local = rp.size - 1
         N_global = N_local * world
         del rp, ci, va
@@ -271,6 +308,8 @@ def main():
     t_phase = [P.last_apply_seconds(i) for i in range(5)]   # averages over the timed steps
     P.set_profiling(False)
     assert bool(np.isfinite(x).all() if args.hostsim else torch.isfinite(x).all()), "ApplyInverse produced non-finite values"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, x, rank, world)
     bytes_all = [P.apply_bytes(i) for i in range(9)]
     bytes_rank0 = list(bytes_all)
     flops_all = [P.setup_flops(i) for i in range(4)]
@@ -370,17 +409,18 @@ def main():
                          "frac": (achieved / 8000.0) if achieved else None, "traffic": traffic,
                          "bytes_per_launch": bytes_launch, "launch_ms": 1e3 * t_launch, "traffic_measured_on": traffic_other},
         }
-        # the setup side of the path (Compute seconds and the FP64 matrix-core rate of K6 / K10): flops of one
-        # numeric Compute counted from the symbolic plans, over the wall time of the recompute (pattern reused: the
-        # numeric work alone); peak = dense FP64 MFMA of MI355X.  MFMA-busy counters of the setup kernels: profiles/.
-        out["setup_roofline"] = {"bound": "mfma", "flops": flops_all[0], "flops_factorisations": flops_all[1],
-                                 "flops_separator_block_inversions": flops_all[2], "flops_transform_and_dropping": flops_all[3],
-                                 "recompute_s": t_recomp, "achieved": flops_all[0] / t_recomp / 1e12 / world if t_recomp > 0 else None,
-                                 "peak": 78.6, "unit": "TFLOP/s", "frac": flops_all[0] / t_recomp / 1e12 / world / 78.6 if t_recomp > 0 else None,
-                                 "note": "whole numeric Compute (host part included), per GPU; flops from the symbolic plans"}
+        if t_recomp is not None:   # (--full)
+            # the setup side of the path (Compute seconds and the FP64 matrix-core rate of K6 / K10): flops of one
+            # numeric Compute counted from the symbolic plans, over the wall time of the recompute (pattern reused: the
+            # numeric work alone); peak = dense FP64 MFMA of MI355X.  MFMA-busy counters of the setup kernels: profiles/.
+            out["setup_roofline"] = {"bound": "mfma", "flops": flops_all[0], "flops_factorisations": flops_all[1],
+                                     "flops_separator_block_inversions": flops_all[2], "flops_transform_and_dropping": flops_all[3],
+                                     "recompute_s": t_recomp, "achieved": flops_all[0] / t_recomp / 1e12 / world if t_recomp > 0 else None,
+                                     "peak": 78.6, "unit": "TFLOP/s", "frac": flops_all[0] / t_recomp / 1e12 / world / 78.6 if t_recomp > 0 else None,
+                                     "note": "whole numeric Compute (host part included), per GPU; flops from the symbolic plans"}
         if krylov:
             out["krylov"] = krylov
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # bounded sample: a 48^3 grid has no third level with sx = cx = 8 (and the serial coarse LU of a larger
             # two-level sample takes minutes to set up, as it does for the reference): two-level sample
             out["cpu_baseline"] = cpu_baseline(args.problem, args.re, args.cpu_n, sx, min(levels, 1), gpu_lib_ok=not args.hostsim)

@@ -8,7 +8,6 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HOSTSIM = os.path.join(ROOT, "tests", "hostsim", "libhymls_mi_hostsim.so")
-REFERENCE = "/root/reference"
 
 
 def pytest_configure(config):

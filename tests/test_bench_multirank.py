@@ -7,6 +7,8 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -18,11 +20,11 @@ def _free_port():
     return p
 
 
-def _run(nproc, extra=()):
+def _run(nproc, extra=(), full=True):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--grid", "16", "--sx", "4", "--levels", "1", "--hostsim", "--no-cpu-baseline"]
-    cmd += list(extra)
+    cmd += (["--full"] if full else []) + list(extra)
     env = dict(os.environ, OMP_NUM_THREADS="1")
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
@@ -56,3 +58,20 @@ def test_bench_single_rank_fields():
     r = _run(1)
     assert r["n_gpus"] == 1 and "1 GPU" in r["config"]["parallelism"]
     assert r["roofline"]["bound"] == "hbm" and r["roofline"]["peak"] == 8000.0
+
+
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """without --full: no recompute, no Krylov solve, no CPU baseline; --dump-outputs writes the last timed step's x, the
+    same in two runs with the same arguments"""
+    outs = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = _run(1, ["--dump-outputs", str(d)], full=False)
+        assert r["steps"] == 2 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["value"] > 0
+        assert r["unit"] == "DoF/s" and r["higher_is_better"] is True and r["dtype"] == "f64"
+        assert "krylov" not in r and "setup_roofline" not in r and r["config"]["recompute_s"] is None
+        assert r["cpu_baseline"] is None
+        x = np.load(str(d / "x.npy"))
+        assert x.dtype == np.float64 and x.shape == (16 * 16 * 16 * 4,) and np.isfinite(x).all() and np.abs(x).max() > 0
+        outs.append(x)
+    assert np.array_equal(outs[0], outs[1])

@@ -22,7 +22,7 @@ from oracle.partition import Params, HierarchicalMap
 from oracle.hymls import Preconditioner as OraclePrec
 
 ALL = (True, True, True)
-REFERENCE = "/root/reference"
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def xml(n, sx, levels, part, per=ALL, extra=None):
@@ -196,12 +196,12 @@ def test_periodic_partition_matches_oracle_gpu(gpu_lib, part, n, sx, per):
     partition_case(gpu_lib, part, n, sx, per)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REFERENCE, "testSuite", "integration_tests", "stokes4_3D.xml")), reason="reference tree not present")
 def test_stokes4_3d_xml_through_the_driver(hostsim_lib):
-    """the reference's own input file through hymls_amd.driver (XML parameter lists, Galeri label, null space type,
-    bordering): its "Targets" list is met"""
+    """the reference's own input file (testSuite/integration_tests/stokes4_3D.xml, committed unchanged as
+    tests/golden/stokes4_3D.xml) through hymls_amd.driver (XML parameter lists, Galeri label, null space type, bordering):
+    its "Targets" list is met"""
     from hymls_amd import driver
-    out = driver.run(os.path.join(REFERENCE, "testSuite", "integration_tests", "stokes4_3D.xml"), lib=hostsim_lib, device="cpu")
+    out = driver.run(os.path.join(GOLD, "stokes4_3D.xml"), lib=hostsim_lib, device="cpu")
     assert out["iterations"] == 1
     assert out["relative_residual"] <= 5e-11 and out["relative_error"] <= 5e-11
 
