@@ -1,6 +1,7 @@
 // capi.cpp -- the C ABI of include/hymls_mi.h on top of LevelSolver.
 #include "../../include/hymls_mi.h"
 #include "precond.hpp"
+#include "capi_internal.hpp"
 #include <chrono>
 #include <cstring>
 
@@ -36,6 +37,18 @@ struct hymls_mi {
   double prof_sum[8] = {0};
   int prof_cnt[8] = {0};
 };
+
+namespace hymls {
+HandleView handle_view(hymls_mi_t* h) {
+  HandleView v;
+  v.top = h->top.get();
+  v.comm = &h->comm;
+  v.ctx = h->ctx;
+  v.computed = h->computed;
+  v.err = &h->err;
+  return v;
+}
+}  // namespace hymls
 
 static double now() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();

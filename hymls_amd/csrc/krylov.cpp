@@ -1,0 +1,421 @@
+// krylov.cpp -- the native Krylov solver of include/hymls_mi_solver.h (the reference's HYMLS::BaseSolver,
+// src/HYMLS_BaseSolver.cpp:104-397, without Belos): restarted GMRES(m) and preconditioned CG on device vectors, with
+// the preconditioner and the operator of a computed hymls_mi handle (LevelSolver::apply_inverse_mv / matvec, on the
+// handle's stream).  The iteration is that of hymls_amd/solver.py step for step, so both take the same number of
+// iterations: classical Gram-Schmidt applied twice, Givens rotations and the small triangular solve on the host,
+// convergence relative to the first residual of the solve.
+//
+// One GMRES iteration on one GPU: ApplyInverse, K x, the three orthogonalisation passes with their device reductions
+// (krylov_hip.hip), the normalisation of the new basis column, and one device-to-host copy of (h1 + h2, ||w||) -- the
+// single synchronisation of the iteration.  Sharded handles add a host all-sum (rank order) after every pass.
+#include "../../include/hymls_mi_solver.h"
+#include "capi_internal.hpp"
+#include "krylov.hpp"
+#include <cmath>
+#include <limits>
+
+using namespace hymls;
+
+struct hymls_mi_solver {
+  hymls_mi_t* h = nullptr;
+  hymls_mi_solver_params p{};
+  std::string err;
+  int its = 0;
+  double achieved = std::numeric_limits<double>::quiet_NaN();
+  // device memory, allocated at the first solve and kept (grown when the row count or the restart length grows)
+  int64_t n = 0, ld = 0;           // rows of this rank, leading dimension of the basis (multiple of 16 doubles)
+  int m_alloc = 0;                 // basis columns allocated
+  double* V = nullptr;             // [(m + 1) * ld]
+  double* vec = nullptr;           // 7 vectors of ld: x, r, w, t, p, prev, staged b
+  double* work = nullptr;          // reduction scratch (dev::KryWork)
+  dev::KryWork ws{};
+  bool have_prev = false;
+  bool profiling = false;
+  double secs[4] = {0, 0, 0, 0};
+  dev::KryTimer* timer = nullptr;
+};
+
+namespace {
+
+struct Run {
+  hymls_mi_solver* s;
+  LevelSolver* L;
+  const Comm* comm;
+  int64_t n, ld;
+  bool dist;
+  double *x, *r, *w, *t, *p, *prev, *bst;
+
+  void mark(int phase, bool begin) { if (s->profiling) dev::kry_mark(s->timer, phase, begin); }
+  void prec(const double* in, double* out) { mark(1, true); L->apply_inverse_mv(in, n, out, n, 1); mark(1, false); }
+  void matvec(const double* in, double* out) { mark(2, true); L->matvec(in, out); mark(2, false); }
+
+  double allsum(double v) {
+    if (!dist) return v;
+    std::vector<double> a{v};
+    comm->allsum(a);
+    return a[0];
+  }
+  double dot(const double* a, const double* b) {
+    dev::kry_dot(n, a, b, s->ws);
+    double v = 0;
+    dev::d2h(&v, s->ws.out, sizeof v);
+    return allsum(v);
+  }
+  double norm(const double* a) { return std::sqrt(dot(a, a)); }
+
+  // w <- (I - V V^T)^2 w over the k columns of V, written to dst; hk[0..k) = h1 + h2, hk[k] = ||dst||
+  void orthogonalize(int k, const double* Vb, int64_t ldv, double* wv, double* dst, double* hk) {
+    orthogonalize_step(s->ws, comm, dist, n, k, Vb, ldv, wv, dst, hk);
+  }
+  static void orthogonalize_step(const dev::KryWork& ws, const Comm* comm, bool dist, int64_t n, int k, const double* Vb,
+                                 int64_t ldv, double* wv, double* dst, double* hk) {
+    dev::kry_pass_a(n, k, Vb, ldv, wv, ws);
+    std::vector<double> h1, h2;
+    if (dist) {
+      h1.resize(k);
+      dev::d2h(h1.data(), ws.h1, k * sizeof(double));
+      comm->allsum(h1);
+      dev::h2d(ws.h1, h1.data(), k * sizeof(double));
+    }
+    dev::kry_pass_b(n, k, Vb, ldv, wv, ws);
+    if (dist) {
+      h2.resize(k);
+      dev::d2h(h2.data(), ws.h2, k * sizeof(double));
+      comm->allsum(h2);
+      dev::h2d(ws.h2, h2.data(), k * sizeof(double));
+    }
+    dev::kry_pass_c(n, k, Vb, ldv, wv, dst, ws);
+    if (dist) {
+      std::vector<double> ss(1);
+      dev::d2h(ss.data(), ws.out + k + 1, sizeof(double));
+      comm->allsum(ss);
+      const double nrm = std::sqrt(ss[0]);
+      dev::h2d(ws.out + k, &nrm, sizeof nrm);
+      for (int j = 0; j < k; j++) hk[j] = h1[j] + h2[j];
+      hk[k] = nrm;
+    }
+  }
+
+  // restarted GMRES (solver.py: Solver._gmres); x holds the start vector
+  void gmres(const double* b, int& its, double& rel) {
+    const hymls_mi_solver_params& P = s->p;
+    const int m = std::min(P.num_blocks, P.max_iters);
+    const bool right = P.right != 0;
+    double* V = s->V;
+    its = 0;
+    rel = std::numeric_limits<double>::infinity();
+    double beta0 = -1.0;
+    std::vector<double> H, cs, sn, g, hk(dev::KRY_KMAX + 2), y;
+    for (int cycle = 0; cycle <= P.max_restarts; cycle++) {
+      if (its > 0 || dot(x, x) > 0.0) {
+        matvec(x, t);
+        mark(3, true); dev::kry_sub(n, b, t, r); mark(3, false);
+      } else {
+        dev::d2d(r, b, n * sizeof(double));
+      }
+      double* rr = r;
+      if (!right) { prec(r, w); rr = w; }
+      const double beta = norm(rr);
+      if (beta0 < 0) beta0 = beta;
+      if (beta0 == 0.0) { rel = 0.0; return; }
+      rel = beta / beta0;
+      if (rel <= P.tol || its >= P.max_iters) break;
+      mark(3, true); dev::kry_div(n, rr, beta, V); mark(3, false);
+      H.assign((size_t)(m + 1) * m, 0.0);   // H[i + (m + 1) * k]
+      cs.assign(m, 0.0); sn.assign(m, 0.0); g.assign(m + 1, 0.0);
+      g[0] = beta;
+      auto Hk = [&](int i, int k) -> double& { return H[(size_t)i + (size_t)(m + 1) * k]; };
+      int k_used = 0;
+      for (int k = 0; k < m; k++) {
+        const double* vk = V + (int64_t)k * ld;
+        if (right) { prec(vk, t); matvec(t, w); }
+        else { matvec(vk, t); prec(t, w); }
+        mark(3, true);
+        double* vn = V + (int64_t)(k + 1) * ld;
+        orthogonalize(k + 1, V, ld, w, vn, hk.data());
+        dev::kry_scale_by(n, vn, s->ws.out + k + 1);   // V[k + 1] = w / ||w|| where ||w|| > 0
+        if (!dist) dev::d2h(hk.data(), s->ws.out, (k + 2) * sizeof(double));
+        mark(3, false);
+        for (int i = 0; i <= k + 1; i++) Hk(i, k) = hk[i];
+        for (int i = 0; i < k; i++) {
+          const double tt = cs[i] * Hk(i, k) + sn[i] * Hk(i + 1, k);
+          Hk(i + 1, k) = -sn[i] * Hk(i, k) + cs[i] * Hk(i + 1, k);
+          Hk(i, k) = tt;
+        }
+        const double d = std::hypot(Hk(k, k), Hk(k + 1, k));
+        cs[k] = Hk(k, k) / d; sn[k] = Hk(k + 1, k) / d;
+        Hk(k, k) = d; Hk(k + 1, k) = 0.0;
+        g[k + 1] = -sn[k] * g[k]; g[k] = cs[k] * g[k];
+        its++; k_used = k + 1;
+        rel = std::fabs(g[k + 1]) / beta0;
+        if (rel <= P.tol || its >= P.max_iters) break;
+      }
+      // y = H(0:k_used, 0:k_used) \ g, upper triangular
+      y.assign(k_used, 0.0);
+      for (int i = k_used - 1; i >= 0; i--) {
+        double v = g[i];
+        for (int j = i + 1; j < k_used; j++) v -= Hk(i, j) * y[j];
+        y[i] = v / Hk(i, i);
+      }
+      dev::h2d(s->ws.h1, y.data(), k_used * sizeof(double));
+      if (right) {
+        mark(3, true); dev::zero(t, n * sizeof(double)); dev::kry_update(n, k_used, V, ld, s->ws.h1, t); mark(3, false);
+        prec(t, w);
+        mark(3, true); dev::kry_add(n, w, x); mark(3, false);
+      } else {
+        mark(3, true); dev::kry_update(n, k_used, V, ld, s->ws.h1, x); mark(3, false);
+      }
+      if (rel <= P.tol || its >= P.max_iters) break;
+    }
+  }
+
+  // preconditioned CG (solver.py: Solver._cg)
+  void cg(const double* b, int& its, double& rel) {
+    const hymls_mi_solver_params& P = s->p;
+    double* z = w;
+    double* q = t;
+    if (dot(x, x) > 0.0) {
+      matvec(x, t);
+      mark(3, true); dev::kry_sub(n, b, t, r); mark(3, false);
+    } else {
+      dev::d2d(r, b, n * sizeof(double));
+    }
+    prec(r, z);
+    dev::d2d(p, z, n * sizeof(double));
+    double rz = dot(r, z);
+    const double r0 = norm(r);
+    its = 0;
+    rel = 1.0;
+    if (r0 == 0.0) { rel = 0.0; return; }
+    while (its < P.max_iters) {
+      matvec(p, q);
+      const double alpha = rz / dot(p, q);
+      mark(3, true);
+      dev::kry_cg_xr(n, alpha, p, q, x, r, s->ws);
+      double rr = 0;
+      dev::d2h(&rr, s->ws.out, sizeof rr);
+      mark(3, false);
+      its++;
+      rel = std::sqrt(allsum(rr)) / r0;
+      if (rel <= P.tol) break;
+      prec(r, z);
+      const double rz_new = dot(r, z);
+      mark(3, true); dev::kry_cg_p(n, rz_new / rz, z, p); mark(3, false);
+      rz = rz_new;
+    }
+  }
+};
+
+uint64_t splitmix64(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+void check_params(const hymls_mi_solver_params& p) {
+  HYMLS_CHECK(p.method == 0 || p.method == 1, -2, "Krylov Method must be GMRES (0) or CG (1)");
+  HYMLS_CHECK(p.initial_vector >= 0 && p.initial_vector <= 2, -2, "Initial Vector must be Zero (0), Random (1) or Previous (2)");
+  HYMLS_CHECK(p.max_iters >= 0 && p.max_restarts >= 0, -2, "Maximum Iterations and Maximum Restarts must not be negative");
+  HYMLS_CHECK(p.method == 1 || (p.num_blocks >= 1 && p.num_blocks <= HYMLS_MI_SOLVER_MAX_BLOCKS), -2,
+              "Num Blocks must lie in 1..256");
+}
+
+void free_buffers(hymls_mi_solver* s) {
+  dev::free(s->V); dev::free(s->vec); dev::free(s->work);
+  s->V = s->vec = s->work = nullptr;
+  s->n = s->ld = 0; s->m_alloc = 0; s->have_prev = false;
+}
+
+}  // namespace
+
+#define SOLVER_BEGIN                           \
+  try {                                        \
+    HandleView hv_ = handle_view(s->h);        \
+    dev::bind(hv_.ctx);
+#define SOLVER_END                                                          \
+  }                                                                         \
+  catch (const hymls::Error& e) { s->err = e.what(); return e.code; }       \
+  catch (const std::exception& e) { s->err = e.what(); return -3; }
+
+extern "C" {
+
+void hymls_mi_solver_default_params(hymls_mi_solver_params* p) {
+  if (!p) return;
+  p->method = 0;
+  p->initial_vector = 0;
+  p->right = 1;
+  p->tol = 1e-8;
+  p->max_iters = 500;
+  p->num_blocks = 250;
+  p->max_restarts = 20;
+  p->seed = 1234;
+}
+
+int hymls_mi_solver_create(hymls_mi_solver_t** out, hymls_mi_t* h, const hymls_mi_solver_params* p) {
+  if (!out || !h) return -2;
+  *out = nullptr;
+  hymls_mi_solver* s = new hymls_mi_solver();
+  s->h = h;
+  if (p) s->p = *p; else hymls_mi_solver_default_params(&s->p);
+  *out = s;
+  SOLVER_BEGIN
+  check_params(s->p);
+  s->timer = dev::kry_timer_create();
+  SOLVER_END
+  return 0;
+}
+
+int hymls_mi_solver_set_params(hymls_mi_solver_t* s, const hymls_mi_solver_params* p) {
+  if (!s || !p) return -2;
+  try { check_params(*p); }
+  catch (const hymls::Error& e) { s->err = e.what(); return e.code; }
+  s->p = *p;
+  return 0;
+}
+
+int hymls_mi_solver_set_tolerance(hymls_mi_solver_t* s, double tol) {
+  if (!s) return -2;
+  s->p.tol = tol;
+  return 0;
+}
+
+int hymls_mi_solver_solve(hymls_mi_solver_t* s, const double* B, int64_t ldb, double* X, int64_t ldx, int nvec, int on_device) {
+  if (!s) return -2;
+  int status = 0;
+  SOLVER_BEGIN
+  HYMLS_CHECK(hv_.computed && hv_.top, -1, "The preconditioner has not yet been computed.");
+  HYMLS_CHECK(hv_.top->border_size() == 0, -2, "the native solver does not solve bordered systems");
+  HYMLS_CHECK(nvec >= 0 && (nvec == 0 || (B && X)), -2, "solve: null B or X");
+  check_params(s->p);
+  LevelSolver* L = hv_.top;
+  const int64_t n = L->num_owned();
+  HYMLS_CHECK(nvec <= 1 || (ldb >= n && ldx >= n), -2, "solve: leading dimension smaller than the number of rows");
+  const bool gm = s->p.method == 0;
+  const int m = gm ? std::min(s->p.num_blocks, std::max(s->p.max_iters, 1)) : 0;
+  // buffers: grown when the problem or the restart length grows; the "Previous" solution survives only if n is unchanged
+  if (n != s->n) {
+    dev::sync();
+    free_buffers(s);
+    s->n = n;
+    s->ld = std::max<int64_t>(16, (n + 15) / 16 * 16);
+    s->vec = (double*)dev::alloc((size_t)7 * s->ld * sizeof(double));
+    s->work = (double*)dev::alloc(dev::kry_work_doubles() * sizeof(double));
+    s->ws.part = s->work;
+    s->ws.h1 = s->ws.part + (size_t)dev::KRY_MAXGRID * dev::KRY_KMAX;
+    s->ws.h2 = s->ws.h1 + dev::KRY_KMAX;
+    s->ws.out = s->ws.h2 + dev::KRY_KMAX;
+  }
+  if (gm && m > s->m_alloc) {
+    dev::sync();
+    dev::free(s->V);
+    s->V = nullptr;
+    s->V = (double*)dev::alloc((size_t)(m + 1) * s->ld * sizeof(double));
+    s->m_alloc = m;
+  }
+  Run R{s, L, hv_.comm, n, s->ld, hv_.comm->distributed()};
+  double* v = s->vec;
+  R.x = v; R.r = v + s->ld; R.w = v + 2 * s->ld; R.t = v + 3 * s->ld; R.p = v + 4 * s->ld;
+  R.prev = v + 5 * s->ld; R.bst = v + 6 * s->ld;
+  std::vector<double> rnd;
+  if (s->p.initial_vector == 1) {
+    const ivec& gids = L->owned_gids();
+    rnd.resize(n);
+    for (int64_t i = 0; i < n; i++) {
+      const uint64_t u = splitmix64(s->p.seed ^ splitmix64((uint64_t)gids[i]));
+      rnd[i] = (double)(u >> 11) * (1.0 / 9007199254740992.0) * 2.0 - 1.0;
+    }
+  }
+  for (int c = 0; c < nvec; c++) {
+    const double* b = B + (int64_t)c * ldb;
+    if (!on_device) { dev::h2d(R.bst, b, n * sizeof(double)); b = R.bst; }
+    if (s->p.initial_vector == 1) dev::h2d(R.x, rnd.data(), n * sizeof(double));
+    else if (s->p.initial_vector == 2 && s->have_prev) dev::d2d(R.x, R.prev, n * sizeof(double));
+    else dev::zero(R.x, n * sizeof(double));
+    R.mark(0, true);
+    int its = 0;
+    double rel = 0;
+    if (gm) R.gmres(b, its, rel); else R.cg(b, its, rel);
+    R.mark(0, false);
+    s->its = its;
+    s->achieved = rel;
+    dev::d2d(R.prev, R.x, n * sizeof(double));
+    s->have_prev = true;
+    if (on_device) dev::d2d(X + (int64_t)c * ldx, R.x, n * sizeof(double));
+    else dev::d2h(X + (int64_t)c * ldx, R.x, n * sizeof(double));
+    if (!(rel <= s->p.tol)) status = -1;
+  }
+  if (s->profiling) dev::kry_collect(s->timer, s->secs);
+  else dev::sync();
+  if (status) {
+    char buf[128];
+    std::snprintf(buf, sizeof buf, "Krylov solver did not converge: %d iterations, relative residual %.3e", s->its, s->achieved);
+    s->err = buf;
+  }
+  SOLVER_END
+  return status;
+}
+
+int hymls_mi_solver_num_iters(const hymls_mi_solver_t* s) { return s ? s->its : 0; }
+double hymls_mi_solver_achieved_tol(const hymls_mi_solver_t* s) { return s ? s->achieved : std::numeric_limits<double>::quiet_NaN(); }
+
+int hymls_mi_solver_set_profiling(hymls_mi_solver_t* s, int on) {
+  if (!s) return -2;
+  SOLVER_BEGIN
+  if (s->timer) {
+    double junk[4] = {0, 0, 0, 0};
+    dev::kry_collect(s->timer, junk);   // drop what was recorded before
+  }
+  s->profiling = on != 0;
+  for (double& t : s->secs) t = 0;
+  SOLVER_END
+  return 0;
+}
+
+double hymls_mi_solver_seconds(const hymls_mi_solver_t* s, int which) {
+  if (!s || which < 0 || which > 3) return 0;
+  return s->secs[which];
+}
+
+int hymls_mi_orthogonalize(hymls_mi_t* h, int64_t n, int32_t k, const double* V, int64_t ldv, double* w, double* hcoef,
+                           double* wnorm) {
+  if (!h) return -2;
+  HandleView hv = handle_view(h);
+  try {
+    dev::bind(hv.ctx);
+    HYMLS_CHECK(n >= 1 && k >= 1 && k <= dev::KRY_KMAX && ldv >= n && V && w && hcoef && wnorm, -2,
+                "orthogonalize: need n >= 1, 1 <= k <= 256, ldv >= n and non-null arrays");
+    double* work = (double*)dev::alloc(dev::kry_work_doubles() * sizeof(double));
+    dev::KryWork ws;
+    ws.part = work;
+    ws.h1 = work + (size_t)dev::KRY_MAXGRID * dev::KRY_KMAX;
+    ws.h2 = ws.h1 + dev::KRY_KMAX;
+    ws.out = ws.h2 + dev::KRY_KMAX;
+    std::vector<double> hk(k + 1);
+    const bool dist = hv.comm->distributed();
+    try {
+      Run::orthogonalize_step(ws, hv.comm, dist, n, k, V, ldv, w, w, hk.data());
+      if (!dist) dev::d2h(hk.data(), ws.out, (k + 1) * sizeof(double));
+    } catch (...) { dev::free(work); throw; }
+    dev::free(work);
+    std::copy(hk.begin(), hk.begin() + k, hcoef);
+    *wnorm = hk[k];
+  } catch (const hymls::Error& e) { *hv.err = e.what(); return e.code; }
+  catch (const std::exception& e) { *hv.err = e.what(); return -3; }
+  return 0;
+}
+
+const char* hymls_mi_solver_last_error(const hymls_mi_solver_t* s) { return s ? s->err.c_str() : "null solver"; }
+
+void hymls_mi_solver_destroy(hymls_mi_solver_t* s) {
+  if (!s) return;
+  try {
+    dev::bind(handle_view(s->h).ctx);
+    dev::sync();
+    free_buffers(s);
+    dev::kry_timer_destroy(s->timer);
+  } catch (...) {}
+  delete s;
+}
+
+}  // extern "C"

@@ -1,0 +1,71 @@
+// krylov.hpp -- device launchers of the native Krylov solver (krylov.cpp): the three-pass ICGS(2) orthogonalisation of
+// GMRES, the basis update x += V y, and the fused vector passes of CG.  The product implements them in krylov_hip.hip;
+// the test-only simulator under tests/krylov_sim implements the same functions with plain loops and the same block
+// decomposition, so that both add the same partial sums in the same order.
+//
+// Reductions are two-stage and fixed-order: stage one writes one partial per workgroup (and per column), stage two
+// sums the partials of each column on the device in a fixed tree.  No atomics: results are bitwise reproducible.
+// Every launcher runs on dev::stream() of the bound context and does not synchronise.
+#pragma once
+#include "device.hpp"
+
+namespace hymls {
+namespace dev {
+
+constexpr int KRY_KMAX = 256;      // columns of one orthogonalisation (= the largest GMRES restart length)
+constexpr int KRY_TILE = 64;       // rows of one basis tile of passes A and B (staged in LDS)
+constexpr int KRY_MAXGRID = 2048;  // workgroups of any stage-one pass (partials per column)
+
+// workgroups of the tiled passes A and B: as many as fit on the chip at once (the LDS tile bounds them), each walks the
+// tiles of its grid stride; rows of the row passes: 256 per workgroup, grid-stride as well
+// (fixed numbers, not queried from the device, so that the partial sums -- and the bits of the result -- do not depend on
+// the card: 256 CUs of an MI355X, 160 KiB of LDS each, at most 8 workgroups of 256 threads per CU)
+constexpr int KRY_LD_TILE = KRY_TILE + 1;   // LDS column stride of a basis tile (odd: conflict-free row and column reads)
+inline size_t kry_tile_lds(int32_t k) { return ((size_t)KRY_LD_TILE * k + KRY_TILE + KRY_KMAX + 4 * KRY_TILE) * sizeof(double); }
+inline int kry_tile_grid(int64_t n, int32_t k) {
+  const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(8, (int64_t)(160 * 1024) / (int64_t)kry_tile_lds(k)));
+  return (int)std::max<int64_t>(1, std::min<int64_t>((n + KRY_TILE - 1) / KRY_TILE, 256 * per_cu));
+}
+inline int kry_row_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, KRY_MAXGRID)); }
+
+// scratch of the reductions, device memory (krylov.cpp allocates it with kry_work_doubles() doubles)
+struct KryWork {
+  double* part;   // [KRY_MAXGRID * KRY_KMAX] stage-one partials
+  double* h1;     // [KRY_KMAX] V^T w of pass A
+  double* h2;     // [KRY_KMAX] V^T w of pass B
+  double* out;    // [KRY_KMAX + 2]: h1 + h2, then ||w|| and ||w||^2 at out[k], out[k + 1]; dot results at out[0]
+};
+inline size_t kry_work_doubles() { return (size_t)KRY_MAXGRID * KRY_KMAX + 2 * KRY_KMAX + KRY_KMAX + 2; }
+
+// pass A: h1 = V^T w over the k columns of V (k <= KRY_KMAX)
+void kry_pass_a(int64_t n, int32_t k, const double* V, int64_t ldv, const double* w, const KryWork& ws);
+// pass B: w <- w - V h1 (h1 from pass A), then h2 = V^T w of the new w, over the same row tile;  out[j] = h1[j] + h2[j]
+void kry_pass_b(int64_t n, int32_t k, const double* V, int64_t ldv, double* w, const KryWork& ws);
+// pass C: dst <- w - V h2, out[k + 1] = dst . dst (this rank's rows), out[k] = its square root (dst may be w itself)
+void kry_pass_c(int64_t n, int32_t k, const double* V, int64_t ldv, const double* w, double* dst, const KryWork& ws);
+// x <- x + V y (y: k device values), the pass-C kernel without the norm
+void kry_update(int64_t n, int32_t k, const double* V, int64_t ldv, const double* y, double* x);
+// x <- x / *d where *d > 0 (device scalar; the column written by pass C, divided by its norm)
+void kry_scale_by(int64_t n, double* x, const double* d);
+// y <- x / s
+void kry_div(int64_t n, const double* x, double s, double* y);
+// r <- b - y
+void kry_sub(int64_t n, const double* b, const double* y, double* r);
+// y <- y + x
+void kry_add(int64_t n, const double* x, double* y);
+// out[0] = x . y
+void kry_dot(int64_t n, const double* x, const double* y, const KryWork& ws);
+// CG: x <- x + alpha p, r <- r - alpha q, out[0] = r . r
+void kry_cg_xr(int64_t n, double alpha, const double* p, const double* q, double* x, double* r, const KryWork& ws);
+// CG: p <- z + beta p
+void kry_cg_p(int64_t n, double beta, const double* z, double* p);
+
+// phase timing of a solve: events recorded on the stream (the simulator takes host clock readings)
+struct KryTimer;
+KryTimer* kry_timer_create();
+void kry_timer_destroy(KryTimer* t);
+void kry_mark(KryTimer* t, int phase, bool begin);     // phase < 4
+void kry_collect(KryTimer* t, double* sum);            // synchronises; adds the seconds of every begin/end pair
+
+}  // namespace dev
+}  // namespace hymls

@@ -1,0 +1,304 @@
+// krylov_hip.hip -- HIP (gfx950 / MI355X) kernels of the native Krylov solver (krylov.hpp, krylov.cpp).
+//
+// One ICGS(2) step w <- (I - V V^T)^2 w over k basis columns (column-major, one contiguous column per Krylov vector)
+// reads the basis three times from HBM:
+//   k_kry_tile<false>   pass A: h1 = V^T w.  A workgroup stages a tile of 64 rows x k columns in LDS (each wave reads
+//                       512 contiguous bytes of one column) and thread j accumulates column j's dot over all tiles of
+//                       its grid stride in a register: one partial per workgroup and column
+//   k_kry_tile<true>    pass B: the same tile first gives w - V h1 for its 64 rows (four quarter sums per row, added in
+//                       a fixed order), then the dots of the new w with the tile that is still in LDS: h2 = V^T w
+//   k_kry_rows<true>    pass C: dst = w - V h2, one row per thread, k coalesced column reads; the norm partials of dst
+//   k_kry_rows<false>   x += V y (solution update), the same kernel without the norm
+//   k_kry_reduce*       stage two of every reduction: the partials of one column summed by one workgroup in a fixed
+//                       tree, on the device, so h1 feeds pass B and h2 pass C without a host round trip
+// plus the vector passes of GMRES and CG.  No atomics anywhere: every result is bitwise reproducible.
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <string>
+#include "krylov.hpp"
+
+namespace hymls {
+namespace dev {
+
+#define KRY_CHECK(call)                                                                    \
+  do {                                                                                     \
+    hipError_t e_ = (call);                                                                \
+    if (e_ != hipSuccess)                                                                  \
+      throw ::hymls::Error(-3, std::string("HIP error: ") + hipGetErrorString(e_) + " at " + \
+                                   __FILE__ + ":" + std::to_string(__LINE__));             \
+  } while (0)
+
+static inline hipStream_t kstream() { return (hipStream_t)stream(); }
+static inline int vec_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, KRY_MAXGRID)); }
+
+// fixed-order sum of the 256 values of red[] (every thread holds one; result in red[0])
+__device__ inline void block_sum256(double* red) {
+  for (int st = 128; st > 0; st >>= 1) {
+    __syncthreads();
+    if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
+  }
+  __syncthreads();
+}
+
+// ---- passes A and B
+template <bool UPD>
+__global__ void __launch_bounds__(256) k_kry_tile(int64_t n, int k, const double* __restrict__ V, int64_t ldv, double* w,
+                                                  const double* __restrict__ h1, double* __restrict__ part) {
+  extern __shared__ double sm[];
+  constexpr int T = KRY_TILE, LT = KRY_LD_TILE;
+  double* Vs = sm;                   // [k][LT]: column j of the tile at Vs[j * LT]
+  double* ws = Vs + (size_t)LT * k;  // [T]
+  double* hs = ws + T;               // [KRY_KMAX]
+  double* red = hs + KRY_KMAX;       // [4][T]
+  const int t = threadIdx.x;
+  if (UPD)
+    for (int j = t; j < k; j += 256) hs[j] = h1[j];
+  double acc = 0.0;
+  const int64_t ntiles = (n + T - 1) / T;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t r0 = tile * T;
+    const int rows = (int)(n - r0 < T ? n - r0 : T);
+    __syncthreads();   // the previous tile is no longer read
+    for (int e = t; e < T * k; e += 256) {
+      const int r = e & (T - 1), j = e / T;
+      Vs[j * LT + r] = r < rows ? V[(int64_t)j * ldv + r0 + r] : 0.0;
+    }
+    if (t < T) ws[t] = t < rows ? w[r0 + t] : 0.0;
+    __syncthreads();
+    if (UPD) {
+      // w - V h1 for the tile: wave q adds the columns j = q mod 4 of row r = lane, the four sums are added in wave order
+      const int r = t & (T - 1), q = t / T;
+      double s = 0.0;
+      for (int j = q; j < k; j += 4) s += Vs[j * LT + r] * hs[j];
+      red[q * T + r] = s;
+      __syncthreads();
+      if (t < T) {
+        const double v = ws[t] - (((red[t] + red[T + t]) + red[2 * T + t]) + red[3 * T + t]);
+        ws[t] = v;   // rows past n: 0 - 0
+        if (t < rows) w[r0 + t] = v;
+      }
+      __syncthreads();
+    }
+    if (t < k) {
+      const double* c = Vs + t * LT;
+#pragma unroll 8
+      for (int r = 0; r < T; r++) acc += c[r] * ws[r];
+    }
+  }
+  if (t < k) part[(int64_t)blockIdx.x * k + t] = acc;
+}
+
+// ---- pass C (NORM) and the solution update
+template <bool NORM>
+__global__ void __launch_bounds__(256) k_kry_rows(int64_t n, int k, const double* __restrict__ V, int64_t ldv,
+                                                  const double* __restrict__ h, const double* w, double* dst,
+                                                  double* __restrict__ part) {
+  __shared__ double hs[KRY_KMAX];
+  __shared__ double red[256];
+  const int t = threadIdx.x;
+  for (int j = t; j < k; j += 256) hs[j] = h[j];
+  __syncthreads();
+  double ss = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + t; i < n; i += (int64_t)gridDim.x * 256) {
+    const double* v = V + i;
+    double s = 0.0;
+#pragma unroll 8
+    for (int j = 0; j < k; j++) s += v[(int64_t)j * ldv] * hs[j];
+    if (NORM) {
+      const double x = w[i] - s;
+      dst[i] = x;
+      ss += x * x;
+    } else {
+      dst[i] = w[i] + s;
+    }
+  }
+  if (NORM) {
+    red[t] = ss;
+    block_sum256(red);
+    if (t == 0) part[blockIdx.x] = red[0];
+  }
+}
+
+// ---- stage two: dst[j] = sum over the nb partials of column j (and dst2[j] = add[j] + dst[j])
+__global__ void __launch_bounds__(256) k_kry_reduce(const double* __restrict__ part, int nb, int k, double* dst,
+                                                    const double* add, double* dst2) {
+  __shared__ double red[256];
+  const int j = blockIdx.x, t = threadIdx.x;
+  double s = 0.0;
+  for (int b = t; b < nb; b += 256) s += part[(int64_t)b * k + j];
+  red[t] = s;
+  block_sum256(red);
+  if (t == 0) {
+    dst[j] = red[0];
+    if (add) dst2[j] = add[j] + red[0];
+  }
+}
+// dst[0] = sqrt(s), dst[1] = s
+__global__ void __launch_bounds__(256) k_kry_reduce_norm(const double* __restrict__ part, int nb, double* dst) {
+  __shared__ double red[256];
+  const int t = threadIdx.x;
+  double s = 0.0;
+  for (int b = t; b < nb; b += 256) s += part[b];
+  red[t] = s;
+  block_sum256(red);
+  if (t == 0) { dst[0] = std::sqrt(red[0]); dst[1] = red[0]; }
+}
+
+// ---- vector passes
+__global__ void __launch_bounds__(256) k_kry_scale_by(int64_t n, double* x, const double* d) {
+  const double s = *d;
+  if (!(s > 0.0)) return;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) x[i] = x[i] / s;
+}
+__global__ void __launch_bounds__(256) k_kry_div(int64_t n, const double* x, double s, double* y) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = x[i] / s;
+}
+__global__ void __launch_bounds__(256) k_kry_sub(int64_t n, const double* b, const double* y, double* r) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) r[i] = b[i] - y[i];
+}
+__global__ void __launch_bounds__(256) k_kry_add(int64_t n, const double* x, double* y) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = y[i] + x[i];
+}
+__global__ void __launch_bounds__(256) k_kry_dot(int64_t n, const double* __restrict__ x, const double* __restrict__ y,
+                                                 double* __restrict__ part) {
+  __shared__ double red[256];
+  double s = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) s += x[i] * y[i];
+  red[threadIdx.x] = s;
+  block_sum256(red);
+  if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+__global__ void __launch_bounds__(256) k_kry_cg_xr(int64_t n, double alpha, const double* __restrict__ p,
+                                                   const double* __restrict__ q, double* __restrict__ x,
+                                                   double* __restrict__ r, double* __restrict__ part) {
+  __shared__ double red[256];
+  double s = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    x[i] = x[i] + alpha * p[i];
+    const double v = r[i] - alpha * q[i];
+    r[i] = v;
+    s += v * v;
+  }
+  red[threadIdx.x] = s;
+  block_sum256(red);
+  if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+__global__ void __launch_bounds__(256) k_kry_cg_p(int64_t n, double beta, const double* __restrict__ z, double* __restrict__ p) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = z[i] + beta * p[i];
+}
+
+static inline void kcheck() { KRY_CHECK(hipGetLastError()); }
+
+template <bool UPD>
+static void tile_pass(int64_t n, int32_t k, const double* V, int64_t ldv, double* w, const KryWork& ws) {
+  if (k < 1 || k > KRY_KMAX) throw Error(-2, "orthogonalisation: 1 <= k <= 256 columns");
+  const int nb = kry_tile_grid(n, k);
+  const size_t shm = kry_tile_lds(k);
+  static thread_local int attr_device = -1;   // the attribute is per device
+  int devno = 0;
+  KRY_CHECK(hipGetDevice(&devno));
+  if (attr_device != devno) {
+    const int most = (int)kry_tile_lds(KRY_KMAX);
+    KRY_CHECK(hipFuncSetAttribute((const void*)k_kry_tile<false>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+    KRY_CHECK(hipFuncSetAttribute((const void*)k_kry_tile<true>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+    attr_device = devno;
+  }
+  hipLaunchKernelGGL(k_kry_tile<UPD>, dim3(nb), dim3(256), shm, kstream(), n, k, V, ldv, w, ws.h1, ws.part);
+  kcheck();
+  if (UPD) hipLaunchKernelGGL(k_kry_reduce, dim3(k), dim3(256), 0, kstream(), ws.part, nb, k, ws.h2, ws.h1, ws.out);
+  else hipLaunchKernelGGL(k_kry_reduce, dim3(k), dim3(256), 0, kstream(), ws.part, nb, k, ws.h1, nullptr, nullptr);
+  kcheck();
+}
+
+void kry_pass_a(int64_t n, int32_t k, const double* V, int64_t ldv, const double* w, const KryWork& ws) {
+  tile_pass<false>(n, k, V, ldv, const_cast<double*>(w), ws);
+}
+void kry_pass_b(int64_t n, int32_t k, const double* V, int64_t ldv, double* w, const KryWork& ws) {
+  tile_pass<true>(n, k, V, ldv, w, ws);
+}
+void kry_pass_c(int64_t n, int32_t k, const double* V, int64_t ldv, const double* w, double* dst, const KryWork& ws) {
+  if (k < 1 || k > KRY_KMAX) throw Error(-2, "orthogonalisation: 1 <= k <= 256 columns");
+  const int nb = kry_row_grid(n);
+  hipLaunchKernelGGL(k_kry_rows<true>, dim3(nb), dim3(256), 0, kstream(), n, k, V, ldv, ws.h2, w, dst, ws.part);
+  kcheck();
+  hipLaunchKernelGGL(k_kry_reduce_norm, dim3(1), dim3(256), 0, kstream(), ws.part, nb, ws.out + k);
+  kcheck();
+}
+void kry_update(int64_t n, int32_t k, const double* V, int64_t ldv, const double* y, double* x) {
+  if (k < 1) return;
+  if (k > KRY_KMAX) throw Error(-2, "basis update: at most 256 columns");
+  hipLaunchKernelGGL(k_kry_rows<false>, dim3(kry_row_grid(n)), dim3(256), 0, kstream(), n, k, V, ldv, y, x, x, nullptr);
+  kcheck();
+}
+void kry_scale_by(int64_t n, double* x, const double* d) {
+  hipLaunchKernelGGL(k_kry_scale_by, dim3(vec_grid(n)), dim3(256), 0, kstream(), n, x, d);
+  kcheck();
+}
+void kry_div(int64_t n, const double* x, double s, double* y) {
+  hipLaunchKernelGGL(k_kry_div, dim3(vec_grid(n)), dim3(256), 0, kstream(), n, x, s, y);
+  kcheck();
+}
+void kry_sub(int64_t n, const double* b, const double* y, double* r) {
+  hipLaunchKernelGGL(k_kry_sub, dim3(vec_grid(n)), dim3(256), 0, kstream(), n, b, y, r);
+  kcheck();
+}
+void kry_add(int64_t n, const double* x, double* y) {
+  hipLaunchKernelGGL(k_kry_add, dim3(vec_grid(n)), dim3(256), 0, kstream(), n, x, y);
+  kcheck();
+}
+void kry_dot(int64_t n, const double* x, const double* y, const KryWork& ws) {
+  const int nb = vec_grid(n);
+  hipLaunchKernelGGL(k_kry_dot, dim3(nb), dim3(256), 0, kstream(), n, x, y, ws.part);
+  kcheck();
+  hipLaunchKernelGGL(k_kry_reduce, dim3(1), dim3(256), 0, kstream(), ws.part, nb, 1, ws.out, nullptr, nullptr);
+  kcheck();
+}
+void kry_cg_xr(int64_t n, double alpha, const double* p, const double* q, double* x, double* r, const KryWork& ws) {
+  const int nb = vec_grid(n);
+  hipLaunchKernelGGL(k_kry_cg_xr, dim3(nb), dim3(256), 0, kstream(), n, alpha, p, q, x, r, ws.part);
+  kcheck();
+  hipLaunchKernelGGL(k_kry_reduce, dim3(1), dim3(256), 0, kstream(), ws.part, nb, 1, ws.out, nullptr, nullptr);
+  kcheck();
+}
+void kry_cg_p(int64_t n, double beta, const double* z, double* p) {
+  hipLaunchKernelGGL(k_kry_cg_p, dim3(vec_grid(n)), dim3(256), 0, kstream(), n, beta, z, p);
+  kcheck();
+}
+
+// ---- phase timing
+struct KryTimer {
+  struct Rec { int phase; bool begin; hipEvent_t ev; };
+  std::vector<Rec> log;
+  std::vector<hipEvent_t> pool;
+};
+KryTimer* kry_timer_create() { return new KryTimer(); }
+void kry_timer_destroy(KryTimer* t) {
+  if (!t) return;
+  for (auto& r : t->log) (void)hipEventDestroy(r.ev);
+  for (auto e : t->pool) (void)hipEventDestroy(e);
+  delete t;
+}
+void kry_mark(KryTimer* t, int phase, bool begin) {
+  hipEvent_t e;
+  if (!t->pool.empty()) { e = t->pool.back(); t->pool.pop_back(); }
+  else KRY_CHECK(hipEventCreate(&e));
+  KRY_CHECK(hipEventRecord(e, kstream()));
+  t->log.push_back({phase, begin, e});
+}
+void kry_collect(KryTimer* t, double* sum) {
+  KRY_CHECK(hipStreamSynchronize(kstream()));
+  hipEvent_t open[4] = {};
+  for (auto& r : t->log) {
+    if (r.begin) open[r.phase] = r.ev;
+    else if (open[r.phase]) {
+      float ms = 0;
+      KRY_CHECK(hipEventElapsedTime(&ms, open[r.phase], r.ev));
+      sum[r.phase] += 1e-3 * ms;
+    }
+  }
+  for (auto& r : t->log) t->pool.push_back(r.ev);
+  t->log.clear();
+}
+
+}  // namespace dev
+}  // namespace hymls

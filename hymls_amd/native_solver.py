@@ -1,0 +1,171 @@
+"""ctypes binding of include/hymls_mi_solver.h: the native Krylov solver (GMRES or CG with the HYMLS preconditioner,
+the reference's ``HYMLS::BaseSolver``) that lives in the library itself, next to the Python ``hymls_amd.Solver``.
+
+``NativeSolver(P, params)`` reads the same parameter dict as ``Solver`` ({"Solver": {...}} or the sublist itself) and
+has the same methods; K is the matrix of the computed preconditioner P and the preconditioner is P's ApplyInverse.
+The solver symbols are bound from ``P._lib`` when the first NativeSolver is made, so libraries without them still
+load through ``hymls_amd.load_library``.
+"""
+import ctypes as C
+
+import numpy as np
+
+from .api import HymlsError
+
+METHODS = {"GMRES": 0, "CG": 1}
+STARTS = {"Zero": 0, "Random": 1, "Previous": 2}
+
+
+class _SolverParams(C.Structure):
+    _fields_ = [("method", C.c_int32), ("initial_vector", C.c_int32), ("right", C.c_int32), ("tol", C.c_double),
+                ("max_iters", C.c_int32), ("num_blocks", C.c_int32), ("max_restarts", C.c_int32), ("seed", C.c_uint64)]
+
+
+_SIG = {
+    "hymls_mi_solver_default_params": (None, [C.POINTER(_SolverParams)]),
+    "hymls_mi_solver_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(_SolverParams)]),
+    "hymls_mi_solver_set_params": (C.c_int, [C.c_void_p, C.POINTER(_SolverParams)]),
+    "hymls_mi_solver_set_tolerance": (C.c_int, [C.c_void_p, C.c_double]),
+    "hymls_mi_solver_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int]),
+    "hymls_mi_solver_num_iters": (C.c_int, [C.c_void_p]),
+    "hymls_mi_solver_achieved_tol": (C.c_double, [C.c_void_p]),
+    "hymls_mi_solver_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
+    "hymls_mi_solver_seconds": (C.c_double, [C.c_void_p, C.c_int]),
+    "hymls_mi_orthogonalize": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "hymls_mi_solver_last_error": (C.c_char_p, [C.c_void_p]),
+    "hymls_mi_solver_destroy": (None, [C.c_void_p]),
+}
+
+
+def bind_solver(lib):
+    """declare the solver symbols on a loaded library (once); AttributeError if it lacks one"""
+    if not getattr(lib, "_hymls_solver_bound", False):
+        for name, (res, args) in _SIG.items():
+            f = getattr(lib, name)
+            f.restype = res
+            f.argtypes = args
+        lib._hymls_solver_bound = True
+    return lib
+
+
+def solver_params(params):
+    """the C parameter struct from a hymls_amd.Solver parameter dict"""
+    sol = params.get("Solver", params)
+    it = sol.get("Iterative Solver", {})
+    p = _SolverParams()
+    method = sol.get("Krylov Method", "GMRES")
+    if method not in METHODS:
+        raise ValueError("Krylov Method must be GMRES or CG")
+    start = sol.get("Initial Vector", "Zero")
+    if start not in STARTS:
+        raise ValueError("Initial Vector must be Zero, Random or Previous")
+    lor = sol.get("Left or Right Preconditioning", "Right")
+    if lor not in ("Left", "Right"):
+        raise ValueError("Left or Right Preconditioning must be Left or Right")
+    p.method, p.initial_vector, p.right = METHODS[method], STARTS[start], int(lor == "Right")
+    p.tol = float(it.get("Convergence Tolerance", 1e-8))
+    p.max_iters = int(it.get("Maximum Iterations", 500))
+    p.num_blocks = int(it.get("Num Blocks", 250))
+    p.max_restarts = int(it.get("Maximum Restarts", 20))
+    p.seed = int(sol.get("Random Seed", 1234))
+    return p
+
+
+class NativeSolver:
+    """K x = b with the library's own Krylov loop; P: a computed hymls_amd.Preconditioner (sharded or not)."""
+
+    def __init__(self, P, params=None):
+        self._P = P
+        self._lib = bind_solver(P._lib)
+        self._s = C.c_void_p()
+        self._params = solver_params(params or {})
+        ierr = self._lib.hymls_mi_solver_create(C.byref(self._s), P._h, C.byref(self._params))
+        if ierr:
+            msg = self._lib.hymls_mi_solver_last_error(self._s).decode() if self._s else "create failed"
+            self.close()
+            raise HymlsError(ierr, msg)
+
+    def _check(self, ierr):
+        if ierr:
+            raise HymlsError(ierr, self._lib.hymls_mi_solver_last_error(self._s).decode())
+
+    # --- reference API (as hymls_amd.Solver)
+    def setParameterList(self, params):
+        """replaces every parameter; a "Previous" start still uses the last solution"""
+        p = solver_params(params)
+        self._check(self._lib.hymls_mi_solver_set_params(self._s, C.byref(p)))
+        self._params = p
+
+    def SetTolerance(self, tol):
+        self._check(self._lib.hymls_mi_solver_set_tolerance(self._s, float(tol)))
+
+    def getNumIter(self):
+        return self._lib.hymls_mi_solver_num_iters(self._s)
+
+    def achievedTol(self):
+        return self._lib.hymls_mi_solver_achieved_tol(self._s)
+
+    def ApplyInverse(self, B, X=None):
+        """solve K X = B.  B: torch tensor on the device (n,) or (nvec, n) (float64, contiguous), or a numpy array (n,)
+        or (n, nvec) in host memory.  Returns X.  Raises RuntimeError if a column did not reach the tolerance (X then
+        holds the last iterate)."""
+        n = self._P._n
+        if hasattr(B, "data_ptr"):
+            import torch
+            assert B.dtype == torch.float64 and B.is_contiguous() and B.shape[-1] == n
+            if X is None:
+                X = torch.empty_like(B)
+            assert X.is_contiguous() and X.shape == B.shape and X.dtype == torch.float64
+            nvec = 1 if B.dim() == 1 else B.shape[0]
+            ierr = self._lib.hymls_mi_solver_solve(self._s, B.data_ptr(), n, X.data_ptr(), n, nvec, 1)
+            out = X
+        else:
+            Bc = np.asfortranarray(np.asarray(B, dtype=np.float64))
+            assert Bc.shape[0] == n
+            Xc = np.empty_like(Bc, order="F")
+            nvec = 1 if Bc.ndim == 1 else Bc.shape[1]
+            ierr = self._lib.hymls_mi_solver_solve(self._s, Bc.ctypes.data, n, Xc.ctypes.data, n, nvec, 0)
+            if X is not None:
+                X[...] = Xc
+                out = X
+            else:
+                out = Xc
+        if ierr == -1:
+            raise RuntimeError(self._lib.hymls_mi_solver_last_error(self._s).decode())
+        self._check(ierr)
+        return out
+
+    # --- measurements
+    def set_profiling(self, on=True):
+        self._check(self._lib.hymls_mi_solver_set_profiling(self._s, int(on)))
+
+    def seconds(self, which=0):
+        """0 whole solve, 1 ApplyInverse, 2 K x, 3 orthogonalisation and vector updates (summed since set_profiling)"""
+        return self._lib.hymls_mi_solver_seconds(self._s, which)
+
+    def close(self):
+        # the solver lives inside P's handle context: nothing to free once P is closed
+        if self._s and self._P._h:
+            self._lib.hymls_mi_solver_destroy(self._s)
+        self._s = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def orthogonalize(P, n, k, V, ldv, w):
+    """one ICGS(2) step of the library (hymls_mi_orthogonalize) on device arrays: w <- (I - V V^T)^2 w in place over
+    the k columns of V (column-major, leading dimension ldv).  V, w: torch tensors (device memory; host memory with the
+    test-only simulator).  Returns (h1 + h2 as a numpy array of k values, ||w||)."""
+    lib = bind_solver(P._lib)
+    h = np.zeros(k)
+    nrm = C.c_double()
+    ierr = lib.hymls_mi_orthogonalize(P._h, n, k, V.data_ptr(), ldv, w.data_ptr(), h.ctypes.data_as(C.POINTER(C.c_double)),
+                                      C.byref(nrm))
+    if ierr:
+        raise HymlsError(ierr, lib.hymls_mi_last_error(P._h).decode())
+    return h, nrm.value

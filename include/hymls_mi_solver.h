@@ -1,0 +1,77 @@
+/* hymls_mi_solver.h -- device-resident Krylov solver on top of a computed hymls_mi handle.
+ *
+ * The counterpart of the reference's HYMLS::BaseSolver (GMRES or CG through Belos with the HYMLS preconditioner
+ * plugged in): K x = b is solved with K applied by hymls_mi_matvec and the preconditioner by ApplyInverse of the same
+ * handle.  Every Krylov vector stays in device memory; the Gram-Schmidt orthogonalisation of GMRES runs in HIP kernels
+ * and the host sees a handful of scalars per iteration.  The iteration is the one of hymls_amd.Solver (Python):
+ * restarted GMRES(m) with classical Gram-Schmidt applied twice and Givens rotations on the host, or preconditioned CG;
+ * convergence is relative to the first residual of the solve.
+ *
+ * Sharded handles (hymls_mi_set_comm / hymls_mi_set_comm_rccl): every rank calls the solver collectively with its
+ * owned rows (hymls_mi_owned_rows order); inner products are summed over the ranks in rank order.
+ *
+ * Kept apart from hymls_mi.h (as the reference keeps HYMLS_BaseSolver.hpp apart from HYMLS_Preconditioner.hpp).
+ */
+#ifndef HYMLS_MI_SOLVER_H
+#define HYMLS_MI_SOLVER_H
+#include <stdint.h>
+#include "hymls_mi.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct hymls_mi_solver hymls_mi_solver_t;
+
+typedef struct hymls_mi_solver_params {
+  int32_t method;          /* "Krylov Method": 0 GMRES, 1 CG                                   (GMRES) */
+  int32_t initial_vector;  /* "Initial Vector": 0 Zero, 1 Random, 2 Previous                   (Zero)  */
+  int32_t right;           /* "Left or Right Preconditioning": 1 Right, 0 Left                 (Right) */
+  double tol;              /* "Convergence Tolerance", relative to the first residual          (1e-8)  */
+  int32_t max_iters;       /* "Maximum Iterations"                                             (500)   */
+  int32_t num_blocks;      /* "Num Blocks": GMRES restart length, 1..HYMLS_MI_SOLVER_MAX_BLOCKS (250)  */
+  int32_t max_restarts;    /* "Maximum Restarts"                                               (20)    */
+  uint64_t seed;           /* "Random": start vector = hash(seed, global row id) in [-1, 1)    (1234)  */
+} hymls_mi_solver_params;
+
+#define HYMLS_MI_SOLVER_MAX_BLOCKS 256
+
+void hymls_mi_solver_default_params(hymls_mi_solver_params* p);
+
+/* h: a handle that has been (or will be, before the first solve) computed; K = the matrix of h, M^{-1} = its ApplyInverse.
+ * The solver keeps a pointer to h: destroy the solver first. */
+int hymls_mi_solver_create(hymls_mi_solver_t** s, hymls_mi_t* h, const hymls_mi_solver_params* p);
+/* replaces every parameter (the reference's setParameterList); the "Previous" solution is kept */
+int hymls_mi_solver_set_params(hymls_mi_solver_t* s, const hymls_mi_solver_params* p);
+int hymls_mi_solver_set_tolerance(hymls_mi_solver_t* s, double tol);
+
+/* Solves K X(:, v) = B(:, v) for v = 0..nvec-1, one column after the other (block size 1).  B, X: column-major with
+ * leading dimensions ldb, ldx (>= this rank's row count); device pointers if on_device, else host memory.
+ * "Previous" starts each column from the solution of the column (or call) solved before it.
+ * Returns 0 when every column converged, -1 when one did not (X then holds the last iterate), < -1 on errors.
+ * num_iters / achieved_tol describe the last column. */
+int hymls_mi_solver_solve(hymls_mi_solver_t* s, const double* B, int64_t ldb, double* X, int64_t ldx, int nvec, int on_device);
+int hymls_mi_solver_num_iters(const hymls_mi_solver_t* s);
+double hymls_mi_solver_achieved_tol(const hymls_mi_solver_t* s);
+
+/* phase timing with events on the stream (adds a synchronisation at the end of every solve while on).
+ * which: 0 whole solve, 1 ApplyInverse, 2 K x, 3 orthogonalisation + updates; seconds summed since profiling was
+ * switched on. */
+int hymls_mi_solver_set_profiling(hymls_mi_solver_t* s, int on);
+double hymls_mi_solver_seconds(const hymls_mi_solver_t* s, int which);
+
+/* One ICGS(2) step on device arrays, the building block of the GMRES iteration (for tests and for callers with an
+ * Arnoldi process of their own):  w <- (I - V V^T)^2 w over the k columns of V (n rows, leading dimension ldv >= n,
+ * 1 <= k <= HYMLS_MI_SOLVER_MAX_BLOCKS).  V and w are device memory; hcoef[k] (= h1 + h2) and *wnorm (= ||w|| after
+ * both passes) are host memory.  On a sharded handle n is this rank's row count and the products are summed over the
+ * ranks (collective). */
+int hymls_mi_orthogonalize(hymls_mi_t* h, int64_t n, int32_t k, const double* V, int64_t ldv, double* w, double* hcoef,
+                           double* wnorm);
+
+const char* hymls_mi_solver_last_error(const hymls_mi_solver_t* s);
+void hymls_mi_solver_destroy(hymls_mi_solver_t* s);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* HYMLS_MI_SOLVER_H */
