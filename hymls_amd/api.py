@@ -87,6 +87,8 @@ def load_library(path=None):
         "hymls_mi_set_testvector": (C.c_int, [H, _F64P]),
         "hymls_mi_initialize": (C.c_int, [H]),
         "hymls_mi_compute": (C.c_int, [H]),
+        "hymls_mi_set_factor_storage": (C.c_int, [H, C.c_int]),
+        "hymls_mi_factor_storage": (C.c_int, [H]),
         "hymls_mi_apply_inverse": (C.c_int, [H, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int]),
         "hymls_mi_set_border": (C.c_int, [H, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
         "hymls_mi_apply_inverse_bordered": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
@@ -249,6 +251,7 @@ def drop_by_value(A, tol=1e-14, kind="RelDropDiag", lib=None):
 
 _EQ = {"Laplace": 0, "Stokes-C": 1}
 _PART = {"Cartesian": 0, "Skew Cartesian": 1}
+_STORAGE = {"double": 64, "single": 32}     # "MI Factor Storage" (include/hymls_mi.h: hymls_mi_set_factor_storage)
 _VT = {"Laplace": 0, "Velocity U": 1, "Velocity V": 2, "Velocity W": 3, "Pressure": 4, "Interior": 5}
 
 
@@ -275,6 +278,10 @@ class Preconditioner:
         self._check(ierr)
         self._n = None
         self._comm = comm
+        # "MI ..." keys: options the reference does not have ("MI Transport" is read by the driver)
+        storage = params.get("Preconditioner", {}).get("MI Factor Storage", "double")
+        if storage != "double":
+            self.SetFactorStorage(storage)
         if comm is not None:
             comm.attach(self)
             px, py, pz = rank_grid
@@ -439,6 +446,17 @@ class Preconditioner:
             X[...] = Xc
             return X
         return Xc
+
+    def SetFactorStorage(self, storage):
+        """"double" (default) or "single": how the interior factor panels that ApplyInverse streams are stored; takes
+        effect at the next Compute() (include/hymls_mi.h: hymls_mi_set_factor_storage)."""
+        if storage not in _STORAGE:
+            raise HymlsError(-2, "'MI Factor Storage' must be \"double\" or \"single\", not %r" % (storage,))
+        self._check(self._lib.hymls_mi_set_factor_storage(self._h, _STORAGE[storage]))
+        return 0
+
+    def FactorStorage(self):
+        return {64: "double", 32: "single"}[self._lib.hymls_mi_factor_storage(self._h)]
 
     # --- BorderedOperator (reference src/HYMLS_BorderedOperator.hpp)
     def SetBorder(self, V, W=None, C_=None):

@@ -122,7 +122,7 @@ struct BatchD {
   double* scratch;       // [chunk][scratch_size]   frontal matrices
   double* sblock;        // [chunk][nS*nS]          separator (Schur) block, col-major
   double* contrib;       // [nb][contrib_size]      solve scratch
-  int32_t* flag;         // device int: set != 0 on zero / non-finite pivot
+  int32_t* flag;         // device int: set != 0 on zero / non-finite pivot (bit 4: FLAG_F32_RANGE, see demote_panels)
   double* tmp;           // [chunk][tmp_stride] dense pivot-piece inverses + panel scratch (big fronts)
   int64_t tmp_stride;
   double* swork;         // [nb][swork_stride] solve workspace: assembled rows, then partial sums
@@ -217,7 +217,10 @@ void repack_fronts(const PlanD& P, const BatchD& B, int32_t b0, int32_t nbc);
 // (forward then backward) with the solution vector and all contribution vectors in LDS;
 // one launch covers every subdomain of every pattern class of a level.
 struct FusedSub {
-  const double* fac;   // factor slab of this subdomain
+  union {
+    const double* fac;   // factor slab of this subdomain
+    const float* fac32;  // ... of a class with FP32 panel storage (the _f32 launchers; same offsets, in elements)
+  };
   int32_t xoff;        // offset of its interior block in the level vector
   int32_t cls;         // index into the PlanD table
 };
@@ -234,6 +237,19 @@ struct FusedIO {
 };
 void interior_solve_fused(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, double* x,
                           const FusedIO* io = nullptr);
+
+// ---- FP32 storage of the panels of the fused solve (option "MI Factor Storage" = "single").  The
+// factorisation is unchanged (FP64 into the FP64 slab, then repack_fronts); demote_panels rounds n entries of the slab to
+// nearest into the FP32 slab, which has the same layout with 4-byte elements.  *flag |= FLAG_F32_RANGE when an entry is
+// not finite or exceeds FLT_MAX in magnitude.  The _f32 forms of the fused solve read FusedSub::fac32, widen every entry
+// to double on load and are otherwise the FP64 kernels: same products, same sums, same order.  round_panels rounds the
+// FP64 slab through float in place (test-only switch HYMLS_MI_ROUND_PANELS=1: the yardstick of the bitwise tests).
+// The host simulator under tests/hostsim has none of these; host code refers to them only under HYMLS_MI_F32_PANELS.
+constexpr int32_t FLAG_F32_RANGE = 4;
+void demote_panels(int64_t n, const double* src, float* dst, int32_t* flag);
+void round_panels(int64_t n, double* slab, int32_t* flag);
+void interior_solve_fused_f32(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, double* x,
+                              const FusedIO* io = nullptr);
 
 // ---- merged level-synchronous solve of the classes that do not fit the fused kernel (large subdomains
 // of the coarser levels): ONE launch per tree level and sweep covers every (class, member, front) of that
@@ -261,6 +277,8 @@ constexpr int NV_MAX = 4;
 // lds_doubles: LDS need for one vector, front_doubles: the share of it that is not replicated per vector
 void interior_solve_fused_mv(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, int32_t front_doubles,
                              double* x, int64_t ldx, int nv);
+void interior_solve_fused_mv_f32(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, int32_t front_doubles,
+                                 double* x, int64_t ldx, int nv);
 void solve_fwd_tasks_mv(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
                         const double* x, double* y, int64_t ld, int nv);
 void solve_bwd_tasks_mv(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,

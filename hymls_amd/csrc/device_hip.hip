@@ -25,6 +25,7 @@
 //     k_big_pivot_blk            pivot pieces (<= 128 x 128): 32 x 32 diagonal blocks factored and inverted in registers,
 //                                everything else as MFMA tile products between LDS operands (k_big_pivot: scalar variant)
 //     k_repack                   packed L-side panels for the classes of the fused solve
+//     k_demote_panels            FP64 slab -> FP32 slab of those classes (optional FP32 panel storage)
 //     k_sblock_*                 separator block init / transformation + dropping in one pass (k_sblock_kept) / extraction
 //     k_gj_* / k_dense_invert    separator blocks: blocked Gauss-Jordan with partial pivoting (32 pivots per panel in registers,
 //                                rank-32 update on the matrix cores) / per-block Gauss-Jordan in LDS or global memory
@@ -39,6 +40,7 @@
 #include <dlfcn.h>
 #include <chrono>
 #include <cstring>
+#include <cfloat>
 #include <array>
 #include <map>
 #include <string>
@@ -2147,6 +2149,50 @@ void repack_fronts(const PlanD& P, const BatchD& B, int32_t b0, int32_t nbc) {
   launch_check();
 }
 
+// ------------------------------------------------------------------ FP32 panel storage (device.hpp)
+// FP64 slab -> FP32 slab, round to nearest (v_cvt_f32_f64 under the default rounding mode), grid-stride.  Entries
+// [head, head + 4 nq) move as two 16-byte loads and one 16-byte store per thread and step (the launcher picks head so
+// that both addresses are aligned); the few entries before and behind them one by one.
+__global__ void __launch_bounds__(256) k_demote_panels(const double* __restrict__ src, float* __restrict__ dst, int64_t n, int64_t head,
+                                                        int32_t* __restrict__ flag) {
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nthr = (int64_t)gridDim.x * 256;
+  bool bad = false;
+  auto cv = [&](double v) { bad |= !(fabs(v) <= (double)FLT_MAX); return (float)v; };   // (also true for a NaN)
+  const int64_t nq = (n - head) / 4;
+  const double2* s2 = (const double2*)(src + head);
+  float4* d4 = (float4*)(dst + head);
+  for (int64_t q = tid; q < nq; q += nthr) {
+    const double2 a = s2[2 * q], b = s2[2 * q + 1];
+    d4[q] = make_float4(cv(a.x), cv(a.y), cv(b.x), cv(b.y));
+  }
+  for (int64_t t = tid; t < head; t += nthr) dst[t] = cv(src[t]);
+  for (int64_t t = head + 4 * nq + tid; t < n; t += nthr) dst[t] = cv(src[t]);
+  if (bad) atomicOr(flag, FLAG_F32_RANGE);
+}
+void demote_panels(int64_t n, const double* src, float* dst, int32_t* flag) {
+  if (n <= 0) return;
+  // entries up to the first 16-byte boundary of dst; src is 32-byte aligned there when both slabs start equally aligned
+  int64_t head = std::min<int64_t>(n, (int64_t)(((16 - (uintptr_t)dst % 16) % 16) / sizeof(float)));
+  if ((uintptr_t)(src + head) % 16 != 0) head = n;   // (never with slabs from hipMalloc: everything one by one)
+  hipLaunchKernelGGL(k_demote_panels, dim3(nblocks(std::max<int64_t>(n / 4, 1), 256, 8192)), dim3(256), 0, g_stream, src, dst, n, head, flag);
+  launch_check();
+}
+// test-only (HYMLS_MI_ROUND_PANELS): the values demote_panels would store, left in the FP64 slab
+__global__ void __launch_bounds__(256) k_round_panels(double* __restrict__ slab, int64_t n, int32_t* __restrict__ flag) {
+  bool bad = false;
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
+    const double v = slab[t];
+    bad |= !(fabs(v) <= (double)FLT_MAX);
+    slab[t] = (double)(float)v;
+  }
+  if (bad) atomicOr(flag, FLAG_F32_RANGE);
+}
+void round_panels(int64_t n, double* slab, int32_t* flag) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_round_panels, dim3(nblocks(n, 256, 8192)), dim3(256), 0, g_stream, slab, n, flag);
+  launch_check();
+}
+
 // ------------------------------------------------------------------ fused interior solve
 // One workgroup per subdomain, level-synchronous: all fronts of one tree level are processed
 // together, one work item per row of [pivot | update rows] (forward) or per pivot row (backward),
@@ -2175,11 +2221,12 @@ __device__ inline PTR uside(PTR base, int packed, int i, int w, int ri, int& c1,
 // (measured and not kept, round 3, profiles/r03_e_*, r03_f_*: requesting the first panel entries of the next phase before
 // the level barrier -- the extra live registers spill at 8 waves per SIMD, 9.7 / 10.9 ms per launch instead of 8.8;
 // non-temporal panel loads -- 13.0 ms: the hint defeats the L2 reuse of the lines neighbouring columns share)
-template <bool PROF>
+// PT: element type of the stored panels (double, or float widened to double on load: FP32 panel storage)
+template <bool PROF, class PT>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) k_interior_fused(const FusedSub* __restrict__ subs, const PlanD* __restrict__ plans,
                                                          double* __restrict__ x, long long* __restrict__ prof, FusedIO io) {
   extern __shared__ double lds[];
-  auto ldp = [](gptr<double> q) { return *q; };
+  auto ldp = [](gptr<PT> q) { return (double)*q; };
   long long tp[6] = {0, 0, 0, 0, 0, 0}, t0 = 0, tstart = 0;
   auto tick = [&](int bucket) { if (PROF) { const long long t = wall_clock64(); tp[bucket] += t - t0; t0 = t; } };
   if (PROF) { t0 = wall_clock64(); tstart = t0; }
@@ -2213,7 +2260,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
   }
   __syncthreads();
   tick(0);
-  const gptr<double> fac = as_global(S.fac);
+  const gptr<PT> fac = as_global((const PT*)(const void*)S.fac);
   const gptr<int32_t> fw_items = as_global(P.fw_items), bw_items = as_global(P.bw_items), fidx = as_global(P.fidx),
                       asm_ptr = as_global(P.asm_ptr), asm_src = as_global(P.asm_src), fw_ptr = as_global(P.fw_ptr), bw_ptr = as_global(P.bw_ptr);
   typedef int v4i __attribute__((ext_vector_type(4)));
@@ -2246,7 +2293,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
         // entry (r, k) of the L-side panel sits at p[c1 * k - tri * k (k + 3) / 2]: plain columns (tri = 0), or the
         // packed strictly-lower triangle for a pivot row of a packed panel (tri = 1)
         int c1, tri;
-        const gptr<double> p = lside(fac + F.lp_off, P.packed, r, w, F.ri, c1, tri);
+        const gptr<PT> p = lside(fac + F.lp_off, P.packed, r, w, F.ri, c1, tri);
         const double* f = Fv + F.lf_off;
         const int kmax = r < w ? r : w;
         double a[4];
@@ -2273,7 +2320,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
         const FusedFront& F = LF[item >> 16];
         const int r = item & 0xffff, w = F.w;
         int c1, tri;
-        const gptr<double> p = lside(fac + F.lp_off, P.packed, r, w, F.ri, c1, tri);
+        const gptr<PT> p = lside(fac + F.lp_off, P.packed, r, w, F.ri, c1, tri);
         const double* f = Fv + F.lf_off;
         const int kmax = r < w ? r : w;
         auto at = [&](int kk) { return ldp(p + (c1 * kk - tri * ((kk * (kk + 3)) >> 1))); };
@@ -2308,7 +2355,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
         const int i = item & 0xffff, w = F.w, ri = F.ri;
         // entry (i, k), k >= i, of U11^{-1}: column k of the tall panel, or of the packed upper triangle
         int c1, tri;
-        const gptr<double> p = uside(fac + F.lp_off, P.packed, i, w, ri, c1, tri);
+        const gptr<PT> p = uside(fac + F.lp_off, P.packed, i, w, ri, c1, tri);
         const double* Xs = X + F.c0;
         double a[4];
 #pragma unroll
@@ -2322,7 +2369,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
           for (int u = 0; u < 4; u++) a[u] += l[u] * Xs[k + u];
         }
         for (; k < w; k++) a[0] += ldp(p + (c1 * k + tri * ((k * (k + 1)) >> 1))) * Xs[k];
-        const gptr<double> qv = fac + F.q_off + i;
+        const gptr<PT> qv = fac + F.q_off + i;
         const gptr<int32_t> idx = fidx + F.idx_off + w;
         k = 0;
         for (; k + 3 < ri; k += 4) {
@@ -2349,7 +2396,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
         const FusedFront& F = LF[item >> 16];
         const int i = item & 0xffff, w = F.w, ri = F.ri;
         int c1, tri;
-        const gptr<double> p = uside(fac + F.lp_off, P.packed, i, w, ri, c1, tri);
+        const gptr<PT> p = uside(fac + F.lp_off, P.packed, i, w, ri, c1, tri);
         const double* Xs = X + F.c0;
         auto at = [&](int kk) { return ldp(p + (c1 * kk + tri * ((kk * (kk + 1)) >> 1))); };
         int k = i + kg;
@@ -2358,7 +2405,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
           a0 += l0 * Xs[k]; a1 += l1 * Xs[k + KG]; a2 += l2 * Xs[k + 2 * KG]; a3 += l3 * Xs[k + 3 * KG];
         }
         for (; k < w; k += KG) a0 += at(k) * Xs[k];
-        const gptr<double> qv = fac + F.q_off + i;
+        const gptr<PT> qv = fac + F.q_off + i;
         const gptr<int32_t> idx = fidx + F.idx_off + w;
         k = kg;
         for (; k + 3 * KG < ri; k += 4 * KG) {
@@ -2393,15 +2440,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
   }
 }
 
-void interior_solve_fused(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, double* x, const FusedIO* iop) {
+template <class PT>
+static void launch_fused(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, double* x, const FusedIO* iop) {
   const FusedIO io = iop ? *iop : FusedIO();
   if (nsub <= 0) return;
   const size_t shm = (size_t)lds_doubles * sizeof(double);
   if (std::getenv("HYMLS_MI_FUSED_PROF")) {
     // development aid: per-phase wall-clock ticks (100 MHz) of every workgroup, averaged, on stderr
     long long* dprof = (long long*)alloc((size_t)nsub * 8 * sizeof(long long));
-    if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_interior_fused<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL((k_interior_fused<true>), dim3(nsub), dim3(256), shm, g_stream, subs, plans, x, dprof, io);
+    if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_interior_fused<true, PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL((k_interior_fused<true, PT>), dim3(nsub), dim3(256), shm, g_stream, subs, plans, x, dprof, io);
     launch_check();
     std::vector<long long> h((size_t)nsub * 8);
     d2h(h.data(), dprof, h.size() * sizeof(long long));
@@ -2413,9 +2461,15 @@ void interior_solve_fused(int32_t nsub, const FusedSub* subs, const PlanD* plans
                  nsub, (tmax - tmin) / 100.0, sum[0] / nsub / 100, sum[1] / nsub / 100, sum[2] / nsub / 100, sum[3] / nsub / 100, sum[4] / nsub / 100, sum[5] / nsub / 100);
     return;
   }
-  if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_interior_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-  hipLaunchKernelGGL(k_interior_fused<false>, dim3(nsub), dim3(256), shm, g_stream, subs, plans, x, (long long*)nullptr, io);
+  if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_interior_fused<false, PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+  hipLaunchKernelGGL((k_interior_fused<false, PT>), dim3(nsub), dim3(256), shm, g_stream, subs, plans, x, (long long*)nullptr, io);
   launch_check();
+}
+void interior_solve_fused(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, double* x, const FusedIO* iop) {
+  launch_fused<double>(nsub, subs, plans, lds_doubles, x, iop);
+}
+void interior_solve_fused_f32(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, double* x, const FusedIO* iop) {
+  launch_fused<float>(nsub, subs, plans, lds_doubles, x, iop);
 }
 
 // ------------------------------------------------------------------ multi-vector variants (several right-hand sides)
@@ -2432,7 +2486,7 @@ static int mv_group_cap(const char* which) {
   return e ? std::max(1, std::atoi(e)) : NV_MAX;
 }
 
-template <int NV>
+template <int NV, class PT>
 __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __restrict__ subs, const PlanD* __restrict__ plans,
                                                             double* __restrict__ x, int64_t ldx) {
   extern __shared__ double lds[];
@@ -2456,7 +2510,7 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
   for (int v = 0; v < NV; v++)
     for (int i = tid; i < nI; i += 256) X[v * nI + i] = xg[v * ldx + i];
   __syncthreads();
-  const gptr<double> fac = as_global(S.fac);            // (pointers out of structures: global memory, see as_global)
+  const gptr<PT> fac = as_global((const PT*)(const void*)S.fac);           // (pointers out of structures: global memory, see as_global)
   const gptr<int32_t> fw_items = as_global(P.fw_items), bw_items = as_global(P.bw_items), fidx = as_global(P.fidx),
                       asm_ptr = as_global(P.asm_ptr), asm_src = as_global(P.asm_src), fw_ptr = as_global(P.fw_ptr), bw_ptr = as_global(P.bw_ptr);
   typedef int v4i __attribute__((ext_vector_type(4)));
@@ -2490,7 +2544,7 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
         const FusedFront& F = LF[item >> 16];
         const int r = item & 0xffff, w = F.w;
         int c1, tri;
-        const gptr<double> p = lside(fac + F.lp_off, P.packed, r, w, F.ri, c1, tri);
+        const gptr<PT> p = lside(fac + F.lp_off, P.packed, r, w, F.ri, c1, tri);
         const double* f = Fv + F.lf_off;
         const int kmax = r < w ? r : w;
         double a[4][NV];    // (the accumulation order of the single-vector kernel: bitwise the same column)
@@ -2530,7 +2584,7 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
         const FusedFront& F = LF[item >> 16];
         const int r = item & 0xffff, w = F.w;
         int c1, tri;
-        const gptr<double> p = lside(fac + F.lp_off, P.packed, r, w, F.ri, c1, tri);
+        const gptr<PT> p = lside(fac + F.lp_off, P.packed, r, w, F.ri, c1, tri);
         const double* f = Fv + F.lf_off;
         const int kmax = r < w ? r : w;
         auto at = [&](int kk) { return p[c1 * kk - tri * ((kk * (kk + 3)) >> 1)]; };
@@ -2575,7 +2629,7 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
         const FusedFront& F = LF[item >> 16];
         const int i = item & 0xffff, w = F.w, ri = F.ri;
         int c1, tri;
-        const gptr<double> p = uside(fac + F.lp_off, P.packed, i, w, ri, c1, tri);
+        const gptr<PT> p = uside(fac + F.lp_off, P.packed, i, w, ri, c1, tri);
         const double* Xs = X + F.c0;
         double a[4][NV];
 #pragma unroll
@@ -2597,7 +2651,7 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
 #pragma unroll
           for (int v = 0; v < NV; v++) a[0][v] += l * Xs[v * nI + k];
         }
-        const gptr<double> qv = fac + F.q_off + i;
+        const gptr<PT> qv = fac + F.q_off + i;
         const gptr<int32_t> idx = fidx + F.idx_off + w;
         k = 0;
         for (; k + 3 < ri; k += 4) {
@@ -2635,7 +2689,7 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
         const FusedFront& F = LF[item >> 16];
         const int i = item & 0xffff, w = F.w, ri = F.ri;
         int c1, tri;
-        const gptr<double> p = uside(fac + F.lp_off, P.packed, i, w, ri, c1, tri);
+        const gptr<PT> p = uside(fac + F.lp_off, P.packed, i, w, ri, c1, tri);
         const double* Xs = X + F.c0;
         auto at = [&](int kk) { return p[c1 * kk + tri * ((kk * (kk + 1)) >> 1)]; };
         int k = i + kg;
@@ -2652,7 +2706,7 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
 #pragma unroll
           for (int v = 0; v < NV; v++) a0[v] += l * Xs[v * nI + k];
         }
-        const gptr<double> qv = fac + F.q_off + i;
+        const gptr<PT> qv = fac + F.q_off + i;
         const gptr<int32_t> idx = fidx + F.idx_off + w;
         k = kg;
         for (; k + 3 * KG < ri; k += 4 * KG) {
@@ -2690,15 +2744,16 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
     for (int i = tid; i < nI; i += 256) xg[v * ldx + i] = X[v * nI + i];
 }
 
-template <int NV>
+template <int NV, class PT>
 static void launch_fused_mv(int32_t nsub, const FusedSub* subs, const PlanD* plans, size_t shm, double* x, int64_t ldx) {
-  if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_interior_fused_mv<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-  hipLaunchKernelGGL(k_interior_fused_mv<NV>, dim3(nsub), dim3(256), shm, g_stream, subs, plans, x, ldx);
+  if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_interior_fused_mv<NV, PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+  hipLaunchKernelGGL((k_interior_fused_mv<NV, PT>), dim3(nsub), dim3(256), shm, g_stream, subs, plans, x, ldx);
   launch_check();
 }
 // lds_doubles: LDS need of one vector; front_doubles: the part of it that holds the front descriptors (not replicated)
-void interior_solve_fused_mv(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, int32_t front_doubles,
-                             double* x, int64_t ldx, int nv) {
+template <class PT>
+static void fused_mv_groups(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, int32_t front_doubles,
+                            double* x, int64_t ldx, int nv) {
   if (nsub <= 0 || nv <= 0) return;
   const size_t per = (size_t)(lds_doubles - front_doubles) * sizeof(double), fixed = (size_t)front_doubles * sizeof(double);
   int v = 0;
@@ -2706,11 +2761,19 @@ void interior_solve_fused_mv(int32_t nsub, const FusedSub* subs, const PlanD* pl
     int g = nv - v >= 4 ? 4 : (nv - v >= 2 ? 2 : 1);
     while (g > 1 && (per * g + fixed > LDS_LIMIT_BYTES || g > mv_group_cap("FUSED"))) g >>= 1;
     double* xv = x + (int64_t)v * ldx;
-    if (g == 4) launch_fused_mv<4>(nsub, subs, plans, per * 4 + fixed, xv, ldx);
-    else if (g == 2) launch_fused_mv<2>(nsub, subs, plans, per * 2 + fixed, xv, ldx);
-    else interior_solve_fused(nsub, subs, plans, lds_doubles, xv, nullptr);
+    if (g == 4) (launch_fused_mv<4, PT>)(nsub, subs, plans, per * 4 + fixed, xv, ldx);
+    else if (g == 2) (launch_fused_mv<2, PT>)(nsub, subs, plans, per * 2 + fixed, xv, ldx);
+    else launch_fused<PT>(nsub, subs, plans, lds_doubles, xv, nullptr);
     v += g;
   }
+}
+void interior_solve_fused_mv(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, int32_t front_doubles,
+                             double* x, int64_t ldx, int nv) {
+  fused_mv_groups<double>(nsub, subs, plans, lds_doubles, front_doubles, x, ldx, nv);
+}
+void interior_solve_fused_mv_f32(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, int32_t front_doubles,
+                                 double* x, int64_t ldx, int nv) {
+  fused_mv_groups<float>(nsub, subs, plans, lds_doubles, front_doubles, x, ldx, nv);
 }
 
 // merged level-synchronous solve, NV columns (k_lvl_fwd / k_lvl_bwd with the LDS vectors and accumulators replicated;

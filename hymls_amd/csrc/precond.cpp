@@ -109,6 +109,27 @@ void drop_by_value(const Csr& A, double tol, int kind, Csr& R) {
 // ------------------------------------------------------------------ BatchedLU
 BatchedLU::~BatchedLU() {
   for (void* p : owned) dev::free(p);
+  dev::free(factor32);
+}
+
+void BatchedLU::release_factor() {
+  if (!batch.factor) return;
+  owned.erase(std::remove(owned.begin(), owned.end(), (void*)batch.factor), owned.end());
+  dev::free(batch.factor);
+  batch.factor = nullptr;
+}
+void BatchedLU::hold_factor() {
+  if (batch.factor) return;
+  batch.factor = (double*)dev::alloc(factor_bytes((int64_t)members.size(), plan.factor_size));
+  owned.push_back(batch.factor);
+}
+void BatchedLU::hold_factor32() {
+  if (!factor32) factor32 = (float*)dev::alloc(factor_bytes((int64_t)members.size(), plan.factor_size) / 2);
+}
+void BatchedLU::release_factor32() { dev::free(factor32); factor32 = nullptr; }
+double BatchedLU::resident_bytes() const {
+  const double fb = (double)factor_bytes((int64_t)members.size(), plan.factor_size);
+  return (batch.factor ? fb : 0.0) + (factor32 ? fb / 2 : 0.0);
 }
 
 // members per factorisation pass and the doubles of frontal scratch / separator blocks / pivot-piece workspace a pass borrows
@@ -663,6 +684,7 @@ void DirectSolver::add_stats(ApplyStats& st, bool) const {
   st.bytes_coarse += 8.0 * lu_->plan.nnz_factor + 8.0 * 4 * n_;
   st.bytes_coarse_sparse += 12.0 * lu_->plan.nnz_sparse + 24.0 * n_ + 8.0 * 4 * n_;
   st.flops_factor += (double)lu_->plan.flops_factor;
+  st.bytes_resident += lu_->resident_bytes();
 }
 
 // ------------------------------------------------------------------ LevelSolver
@@ -1848,7 +1870,7 @@ void LevelSolver::build_schur_setup() {
     fused_front_lds_ = std::max(fused_front_lds_, (int32_t)(C.lu.plan.fronts.size() * 6 + 1));
     fused_vec_lds_ = std::max(fused_vec_lds_, need - (int32_t)(C.lu.plan.fronts.size() * 6 + 1));
     for (size_t b = 0; b < C.lu.members.size(); b++)
-      subs.push_back(dev::FusedSub{C.lu.batch.factor + (int64_t)b * C.lu.plan.factor_size, C.lu.h_xoff[b], (int32_t)c});
+      subs.push_back(dev::FusedSub{{C.lu.batch.factor + (int64_t)b * C.lu.plan.factor_size}, C.lu.h_xoff[b], (int32_t)c});
   }
   // (Measured and dropped, gpurun_out/r3ao: the workgroups of the heaviest classes first, so that the tail of the launch consists
   // of the light ones -- 8.89 against 8.81 ms per launch, averaged over both set-up orders of the A/B harness.)
@@ -2043,6 +2065,48 @@ void LevelSolver::next_test_vector(dvec& tvn) const {
   }
 }
 
+// Storage of the panels of the fused classes for this Compute.  FP64: the slab of upload(), as ever.
+// FP32: the factorisation still writes the FP64 slab, every chunk is demoted into the FP32 slab right after its repack, and
+// finish_factor_storage() gives the FP64 slab back until the next Compute.  d_fsubs_ points into whichever the solve reads.
+void LevelSolver::prepare_factor_storage() {
+#ifdef HYMLS_MI_F32_PANELS
+  HYMLS_CHECK(factor_bits_ == 64 || bm_ == 0, -99, "FP32 factor storage is not implemented for bordered systems "
+                                                   "(the transposed solve reads the FP64 panels)");
+  if (factor_bits_ == 64 && fsubs_bits_ == 64) return;
+  dev::sync();   // (slabs may still be read by an ApplyInverse in flight)
+  std::vector<dev::FusedSub> subs;
+  for (size_t c = 0; c < cls_.size(); c++) {
+    if (!cls_fused_[c]) continue;
+    BatchedLU& lu = cls_[c]->lu;
+    lu.hold_factor();
+    if (factor_bits_ == 32) lu.hold_factor32(); else lu.release_factor32();
+    for (size_t b = 0; b < lu.members.size(); b++) {
+      dev::FusedSub s{};
+      if (factor_bits_ == 32) s.fac32 = lu.factor32 + (int64_t)b * lu.plan.factor_size;
+      else s.fac = lu.batch.factor + (int64_t)b * lu.plan.factor_size;
+      s.xoff = lu.h_xoff[b]; s.cls = (int32_t)c;
+      subs.push_back(s);
+    }
+  }
+  if (factor_bits_ != fsubs_bits_) {
+    HYMLS_CHECK((int32_t)subs.size() == n_fsubs_, -3, "fused solve table: inconsistent size");
+    if (!subs.empty()) dev::h2d(d_fsubs_, subs.data(), subs.size() * sizeof(dev::FusedSub));
+    fsubs_bits_ = factor_bits_;
+  }
+#else
+  HYMLS_CHECK(factor_bits_ == 64, -99, "this build has no FP32 panel kernels");
+#endif
+}
+
+void LevelSolver::finish_factor_storage() {
+#ifdef HYMLS_MI_F32_PANELS
+  if (fsubs_bits_ != 32) return;
+  dev::sync();   // (the demotions read the FP64 slabs)
+  for (size_t c = 0; c < cls_.size(); c++)
+    if (cls_fused_[c]) cls_[c]->lu.release_factor();
+#endif
+}
+
 void LevelSolver::compute() {
   HYMLS_CHECK(initialized_, -1, "level not initialized");
   dev::Range range("Preconditioner", level_ + 1, "Compute");
@@ -2054,6 +2118,7 @@ void LevelSolver::compute() {
     std::fprintf(stderr, "[hymls_mi] rank %d level %d compute: %-28s %.2f s\n", comm_->rank, level_, what, wall() - t0);
     t0 = wall();
   };
+  prepare_factor_storage();
   dev::h2d(d_kval_, K_.val.data(), K_.val.size() * sizeof(double));
   mv_stale_ = true;
   dev::gather((int64_t)a12_col_.size(), d_a12_src_, d_kval_, d_a12_val_);
@@ -2082,6 +2147,10 @@ void LevelSolver::compute() {
   auto range_mb = std::make_unique<dev::Range>("MatrixBlock", level_ + 1, "Compute");
   if (side || chunk_streams) dev::fork_streams();
   int64_t chunk_id = 0;
+#ifdef HYMLS_MI_F32_PANELS
+  // test-only: FP64 storage of the values FP32 storage would hold (the yardstick of the bitwise tests)
+  const bool round_panels = std::getenv("HYMLS_MI_ROUND_PANELS") && std::atoi(std::getenv("HYMLS_MI_ROUND_PANELS")) != 0;
+#endif
   // (coarser levels: classes in their order, round robin over the side streams.  Measured and not kept: classes in descending
   // order of work on the least loaded stream -- 1.36 s instead of 1.13 s for level 2 of the 256^3 run with four streams, the
   // largest classes then run at the same time; six or eight streams: 1.12 s and 15-27 GiB more memory.)
@@ -2094,6 +2163,13 @@ void LevelSolver::compute() {
       if (chunk_streams) dev::use_stream(1 + (int)(chunk_id++ % chunk_streams));
       C.lu.factor_chunk(d_kval_, b0, nbc);
       C.lu.repack_chunk(b0, nbc);
+#ifdef HYMLS_MI_F32_PANELS
+      if (cls_fused_[c] && (fsubs_bits_ == 32 || round_panels)) {
+        const int64_t off = (int64_t)b0 * C.lu.plan.factor_size, len = (int64_t)nbc * C.lu.plan.factor_size;
+        if (fsubs_bits_ == 32) dev::demote_panels(len, C.lu.batch.factor + off, C.lu.factor32 + off, C.lu.batch.flag);
+        else dev::round_panels(len, C.lu.batch.factor + off, C.lu.batch.flag);
+      }
+#endif
       if (C.pat.nS == 0) continue;
       if (!direct_schur_) {
         // orthogonal transformation + dropping: only the kept entries are formed, in one read pass over the block
@@ -2115,15 +2191,22 @@ void LevelSolver::compute() {
   if (side || chunk_streams) dev::join_streams();
   range_mb.reset();
   dev::Range range_sp("SchurPreconditioner", level_ + 1, "Compute");
-  int32_t bad = 0, grown = 0;
+  int32_t bad = 0, grown = 0, range32 = 0;
   double growth = 0.0;
-  for (auto& cp : cls_) { double g = 0.0; const int32_t f = cp->lu.check_flag(&g); bad |= (f & 1); grown |= (f & 2) >> 1; growth = std::max(growth, g); }
+  for (auto& cp : cls_) {
+    double g = 0.0;
+    const int32_t f = cp->lu.check_flag(&g);
+    bad |= (f & 1); grown |= (f & 2) >> 1; range32 |= (f & dev::FLAG_F32_RANGE) != 0; growth = std::max(growth, g);
+  }
   if (verbose) std::fprintf(stderr, "[hymls_mi] rank %d level %d compute: largest element growth of a pivot block %.3g\n", comm_->rank, level_, growth);
   // (collective: every rank has to reach the exchanges below, so errors are agreed on first)
   HYMLS_CHECK(comm_->allsum(bad) == 0, -4, "subdomain factorisation hit a zero or non-finite pivot (level " +
                                                std::to_string(level_) + ")");
   HYMLS_CHECK(comm_->allsum(grown) == 0, -4, "subdomain factorisation without pivoting is unstable for this matrix: element growth " +
                                              std::to_string(growth) + " > 1e8 (level " + std::to_string(level_) + "); the factor would be inaccurate");
+  HYMLS_CHECK(comm_->allsum(range32) == 0, -4, "FP32 factor storage: a factor panel entry of level " + std::to_string(level_) +
+                                               " is not finite or exceeds the largest float (3.4e38); use FP64 storage for this matrix");
+  finish_factor_storage();
   lap("factor + transform + extract");
   compute_border();
   exchange_records();
@@ -2224,6 +2307,7 @@ void LevelSolver::compute() {
     next_level_->profiling = false;  // phases are reported for the top level only
     lap("next level initialize");
     set_next_border();
+    next_level_->set_factor_bits(factor_bits_);
     next_level_->compute();
     lap("next level compute");
   } else {
@@ -2246,6 +2330,12 @@ void LevelSolver::interior_solve(double* x1) { interior_solve_mv(x1, n1_ + ngi_,
 void LevelSolver::interior_solve_mv(double* x1, int64_t ld, int nv) {
   dev::Range range("MatrixBlock", level_ + 1, "ApplyInverse");
   if (n_fsubs_ > 0) {
+#ifdef HYMLS_MI_F32_PANELS
+    if (fsubs_bits_ == 32) {
+      if (nv == 1) dev::interior_solve_fused_f32(n_fsubs_, d_fsubs_, d_fplans_, fused_lds_, x1);
+      else dev::interior_solve_fused_mv_f32(n_fsubs_, d_fsubs_, d_fplans_, fused_vec_lds_ + fused_front_lds_, fused_front_lds_, x1, ld, nv);
+    } else
+#endif
     if (nv == 1) dev::interior_solve_fused(n_fsubs_, d_fsubs_, d_fplans_, fused_lds_, x1);
     else dev::interior_solve_fused_mv(n_fsubs_, d_fsubs_, d_fplans_, fused_vec_lds_ + fused_front_lds_, fused_front_lds_, x1, ld, nv);
   }
@@ -2605,7 +2695,9 @@ void LevelSolver::matvec(const double* x, double* y) {
 void LevelSolver::add_stats(ApplyStats& st, bool as_coarse) const {
   double f = 0, fs = 0, sp = 0, sep = 0, vec = 0;
   for (auto& cp : cls_) {
-    f += 2.0 * 8.0 * (double)cp->lu.plan.nnz_factor * (double)cp->lu.members.size();
+    // (both sweeps of both solves; 4 B per entry where the panels are stored in FP32)
+    f += 2.0 * (cp->lu.factor32 ? 4.0 : 8.0) * (double)cp->lu.plan.nnz_factor * (double)cp->lu.members.size();
+    st.bytes_resident += cp->lu.resident_bytes();
     fs += 2.0 * (12.0 * (double)cp->lu.plan.nnz_sparse + 24.0 * cp->lu.plan.nI) * (double)cp->lu.members.size();
   }
   sp = 12.0 * (double)(a12_col_.size() + a21_col_.size()) + 4.0 * (n1_ + n2_ + 2);

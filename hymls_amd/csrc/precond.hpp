@@ -29,6 +29,8 @@ struct ApplyStats {
   // flops_transform: orthogonal transformation + dropping of the separator blocks, 4 nS^2 per subdomain (one fused pass,
   // K8; the reference's two-sided Householder per group costs 4 nS^2 x #groups)
   double flops_factor = 0, flops_blocks = 0, flops_transform = 0;
+  // bytes of factor panels (FP64 and FP32 slabs of every level, last-level solver included) held on the device right now
+  double bytes_resident = 0;
 };
 
 // A device allocation made on a helper thread while the setup thread goes on: a hipMalloc of tens of GiB takes about 30 ms per
@@ -99,7 +101,16 @@ struct BatchedLU {
   void bind_scratch();            // point batch.scratch / sblock / tmp into the shared setup arena
   int64_t scratch_need_ = 0, sblock_need_ = 0, tmp_need_ = 0;   // doubles   // after factor_chunk and after the separator block was read
   void solve(double* x) const;    // forward + backward, all members, in place
-  int32_t check_flag(double* growth = nullptr) const;   // flag bits (1 zero pivot, 2 growth) and the largest growth factor
+  int32_t check_flag(double* growth = nullptr) const;   // flag bits (1 zero pivot, 2 growth, 4 FP32 range) and the largest growth factor
+  // FP32 storage of the panels (classes of the fused solve): the FP32 slab, [nb][factor_size] floats.
+  // While it is in use the FP64 slab only exists during Compute: release_factor() gives it back, hold_factor() obtains it
+  // again (same size, new address: whoever keeps pointers into it has to refresh them).
+  float* factor32 = nullptr;
+  void hold_factor();
+  void release_factor();
+  void hold_factor32();
+  void release_factor32();
+  double resident_bytes() const;   // of both slabs, as allocated right now
 };
 
 // tables of the merged level-synchronous solve (device.hpp: solve_fwd_tasks / solve_bwd_tasks) for a set of batches
@@ -215,6 +226,9 @@ class LevelSolver : public Operator {
   void set_border(int m, const double* dV, const double* dW, const double* C) override;
   void apply_inverse_bordered(const double* b, const double* T, double* x, double* S) override;
   bool have_border() const { return bm_ > 0; }
+  // storage of the panels of the fused interior solve, 64 or 32 bits per entry, on this level and every coarser one; takes
+  // effect with the next compute()
+  void set_factor_bits(int bits) { factor_bits_ = bits; }
   int border_size() const { return bm_; }
   int64_t size() const override { return global_n_; }
   void add_stats(ApplyStats& st, bool as_coarse) const override;
@@ -313,6 +327,10 @@ class LevelSolver : public Operator {
   dev::PlanD* d_fplans_ = nullptr;
   int32_t n_fsubs_ = 0, fused_lds_ = 0, fused_front_lds_ = 0, fused_vec_lds_ = 0;
   std::vector<char> cls_fused_;
+  int factor_bits_ = 64;   // wanted (set_factor_bits)
+  int fsubs_bits_ = 64;    // what the slabs and d_fsubs_ hold since the last compute()
+  void prepare_factor_storage();   // start of compute(): slabs and d_fsubs_ for factor_bits_
+  void finish_factor_storage();    // after the factorisation: range check, FP64 slabs of FP32 classes released
   // merged level solve tables (classes too large for the fused kernel)
   std::vector<char> cls_merged_;
   MergedSolve merged_;

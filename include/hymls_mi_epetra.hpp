@@ -28,6 +28,8 @@
 //     "MI Transport": "RCCL" (default: the library's ncclSend/ncclRecv groups on its stream, bootstrapped over MPI) or
 //     "MPI" (MPI_Alltoallv with host staging: any MPI library, several ranks per GPU, the test-only host simulator);
 //     include/hymls_mi_mpi.h holds both.
+// One more "Preconditioner" key the reference does not have: "MI Factor Storage" = "double" (default) or "single", the
+// storage of the interior factor panels ApplyInverse streams (hymls_mi_set_factor_storage in hymls_mi.h).
 #ifndef HYMLS_MI_EPETRA_HPP
 #define HYMLS_MI_EPETRA_HPP
 
@@ -123,6 +125,10 @@ class Preconditioner : public Ifpack_Preconditioner {
       p_.fix_gid[p_.nfix++] = prec.get(key, -1);
     }
     transport_ = prec.get("MI Transport", std::string("RCCL"));
+    // storage of the interior factor panels (include/hymls_mi.h: hymls_mi_set_factor_storage)
+    const std::string storage = prec.get("MI Factor Storage", std::string("double"));
+    if (storage != "double" && storage != "single") return fail(-2, "\"MI Factor Storage\" has to be \"double\" or \"single\"");
+    factor_bits_ = storage == "single" ? 32 : 64;
     have_params_ = true;
     Release();   // new parameters: everything is rebuilt by the next Initialize
     return 0;
@@ -139,6 +145,8 @@ class Preconditioner : public Ifpack_Preconditioner {
     const bool fresh = !h_;
     if (fresh) {
       ierr = hymls_mi_create(&h_, &p_, device_);
+      if (ierr) return keep_error(ierr);
+      ierr = hymls_mi_set_factor_storage(h_, factor_bits_);
       if (ierr) return keep_error(ierr);
       if (distributed_) {
         ierr = AttachComm();
@@ -406,6 +414,7 @@ class Preconditioner : public Ifpack_Preconditioner {
   int device_;
   bool have_params_ = false, have_border_ = false, matrix_dirty_ = true, distributed_ = false;
   std::string transport_ = "RCCL";
+  int factor_bits_ = 64;   // "MI Factor Storage": "double" (64) or "single" (32)
   Teuchos::RCP<Epetra_Map> overlapMap_, ownedMap_;            // required rows / owned rows of this rank
   Teuchos::RCP<Epetra_Import> rowImporter_, vecImporter_;     // matrix row map -> overlapMap_ / ownedMap_
 #ifdef HYMLS_MI_HAVE_MPI
