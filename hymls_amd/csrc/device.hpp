@@ -135,7 +135,12 @@ void scatter(int64_t n, const int32_t* idx, const double* src, double* dst);    
 void scatter_add(int64_t n, const int32_t* idx, const double* src, double* dst); // dst[idx[i]] += src[i] (atomic: idx may repeat)
 void axpby(int64_t n, double a, const double* x, double b, double* y);           // y = a x + b y
 void scale_copy(int64_t n, double a, const double* x, double* y);                // y = a x
-// y = alpha * A x + beta * y, CSR with 32-bit indices
+// y = alpha * A x + beta * y, CSR with 32-bit indices.  Lanes that share a row (and with them the order in which a row is
+// summed): from the average row length when the caller passes nnz, 4 otherwise (rows here have 1-33 entries)
+inline int spmv_lanes(int32_t nrows, int64_t nnz_hint) {
+  const double avg = nnz_hint >= 0 ? (double)nnz_hint / nrows : 8.0;
+  return avg < 2.5 ? 1 : (avg < 5.0 ? 2 : (avg < 20.0 ? 4 : 8));
+}
 void spmv(int32_t nrows, const int32_t* rowptr, const int32_t* col, const double* val,
           const double* x, double* y, double alpha, double beta, int64_t nnz_hint = -1);
 // out[e] = sum_{t in [ptr[e],ptr[e+1])} in[idx[t]]   (deterministic pull-assembly)
@@ -225,12 +230,17 @@ struct FusedSub {
   int32_t cls;         // index into the PlanD table
 };
 constexpr int FUSED_MAX_ITEMS = 2048;  // max work items (rows) of one tree level handled by the fused kernel
-// optional fusion of the neighbouring vector kernels into the load / store of the fused solve:
+// the neighbouring vector kernels of ApplyInverse inside the load / store of the fused solve (LevelSolver::apply_inverse_mv
+// passes it for one vector when every interior row of the level is solved by this kernel; nullptr = plain solve in place):
 //   in  = 0: right-hand side = x (in place)      1: x_rhs[i] = b[perm[i]] (the entry gather of ApplyInverse)
-//         2: x_rhs[i] = (A x2)[i], A in CSR over the interior rows (y1 = A12 x2 of the second solve)
+//         2: x_rhs[i] = (A x2)[i], A in CSR over the interior rows (y1 = A12 x2 of the second solve), every row summed
+//            by a_lanes lanes the way spmv() does it with alpha = 1, beta = 0 (a_lanes = spmv_lanes(rows, nnz))
 //   out = 0: x[i] = solution                     1: user[perm[i]] = z[i] - solution (x1 -= A11 \ y1 and the exit scatter)
+// Combinations with a kernel: (0, 0), (1, 0) and (2, 1); anything else is an error.  perm, the CSR rows and z are indexed
+// like x (FusedSub::xoff + i); x itself is not touched with in = 2, out = 1.  Results are bitwise those of the separate
+// gather / spmv / axpby / scatter kernels.
 struct FusedIO {
-  int32_t in = 0, out = 0;
+  int32_t in = 0, out = 0, a_lanes = 1;
   const double* b = nullptr; const int32_t* perm = nullptr;
   const int32_t* a_row = nullptr; const int32_t* a_col = nullptr; const double* a_val = nullptr; const double* x2 = nullptr;
   const double* z = nullptr; double* user = nullptr;

@@ -6,6 +6,8 @@
 //     k_interior_fused           one workgroup per subdomain walks its whole assembly tree level by level with
 //                                the solution, the contribution vectors and the front descriptors in LDS; the
 //                                factor panels (column-major or packed, rows on consecutive lanes) are streamed once
+//     k_interior_fused_io        the same with a neighbouring vector pass of ApplyInverse in its load / store (FusedIO):
+//                                gather of b1; A12 x2, x1 -= A11 \ y1 and the scatter of x1
 //     k_lvl_fwd / k_lvl_bwd      subdomains too large for LDS: one launch per tree level for all classes, a task is a
 //                                whole small front or a 64-row tile of a large one
 //     k_solve_* / k_panel_*      the coarse direct solver (one class, one member): small fronts per workgroup,
@@ -376,8 +378,7 @@ void spmv(int32_t nrows, const int32_t* rp, const int32_t* col, const double* va
   if (nrows <= 0) return;
   // lanes per row from the average row length (the CSR arrays live on the device: the caller passes nnz if it
   // knows it; 4 lanes otherwise, rows here have 1-33 nnz)
-  const double avg = nnz_hint >= 0 ? (double)nnz_hint / nrows : 8.0;
-  const int L = avg < 2.5 ? 1 : (avg < 5.0 ? 2 : (avg < 20.0 ? 4 : 8));
+  const int L = spmv_lanes(nrows, nnz_hint);
   const int64_t nt = (int64_t)nrows * L;
   const dim3 grid(nblocks(nt, 256));
   switch (L) {
@@ -2222,9 +2223,30 @@ __device__ inline PTR uside(PTR base, int packed, int i, int w, int ri, int& c1,
 // the level barrier -- the extra live registers spill at 8 waves per SIMD, 9.7 / 10.9 ms per launch instead of 8.8;
 // non-temporal panel loads -- 13.0 ms: the hint defeats the L2 reuse of the lines neighbouring columns share)
 // PT: element type of the stored panels (double, or float widened to double on load: FP32 panel storage)
-template <bool PROF, class PT>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) k_interior_fused(const FusedSub* __restrict__ subs, const PlanD* __restrict__ plans,
-                                                         double* __restrict__ x, long long* __restrict__ prof, FusedIO io) {
+// Rows [0, n) of a CSR product into LDS by the 256 threads of a workgroup, formed exactly as k_spmv<L> forms them with
+// alpha = 1, beta = 0: L consecutive lanes share a row, each adds its entries in CSR order starting from +0.0, the partial
+// sums meet in the same shuffle tree, and s + 0.0 is stored (an empty or cancelling row gives +0.0).  Same bits, then, as
+// the separate kernel with the lane count spmv() picks (spmv_lanes).
+template <int L>
+__device__ __forceinline__ void fused_spmv_rows(int n, int tid, gptr<int32_t> rp, gptr<int32_t> col, gptr<double> val, gptr<double> x, double* y) {
+  const int lane = tid % L, rpb = 256 / L;
+  for (int base = 0; base < n; base += rpb) {     // uniform trip count: every lane of a sub-wave takes part in the shuffles
+    const int row = base + tid / L;
+    double s = 0.0;
+    if (row < n) {
+      const int b = rp[row], e = rp[row + 1];
+      for (int k = b + lane; k < e; k += L) s += val[k] * x[col[k]];
+    }
+#pragma unroll
+    for (int off = L / 2; off > 0; off >>= 1) s += __shfl_down(s, off, L);
+    if (row < n && lane == 0) y[row] = s + 0.0;
+  }
+}
+// IN / OUT: where the right-hand side comes from and where the solution goes (FusedIO, device.hpp), fixed at compile time
+// so that the plain solve carries none of it.  The body is shared by the two kernels below.
+template <bool PROF, class PT, int IN, int OUT>
+__device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__ subs, const PlanD* __restrict__ plans,
+                                                    double* __restrict__ x, long long* __restrict__ prof, const FusedIO io) {
   extern __shared__ double lds[];
   auto ldp = [](gptr<PT> q) { return (double)*q; };
   long long tp[6] = {0, 0, 0, 0, 0, 0}, t0 = 0, tstart = 0;
@@ -2247,15 +2269,22 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
     LF[i] = f;
   }
   double* xg = x + S.xoff;
-  if (io.in == 0) {
+  if (IN == 0) {
     for (int i = tid; i < P.nI; i += 256) X[i] = xg[i];
-  } else if (io.in == 1) {
-    for (int i = tid; i < P.nI; i += 256) X[i] = io.b[io.perm[S.xoff + i]];
+  } else if (IN == 1) {
+    // the entry gather of ApplyInverse (k_gather): b through the permutation
+    const gptr<int32_t> perm = as_global(io.perm) + S.xoff;
+    const gptr<double> b = as_global(io.b);
+    for (int i = tid; i < P.nI; i += 256) X[i] = b[perm[i]];
   } else {
-    for (int i = tid; i < P.nI; i += 256) {
-      double v = 0.0;
-      for (int e = io.a_row[S.xoff + i]; e < io.a_row[S.xoff + i + 1]; e++) v += io.a_val[e] * io.x2[io.a_col[e]];
-      X[i] = v;
+    // y1 = A12 x2 (k_spmv with alpha = 1, beta = 0)
+    const gptr<int32_t> a_row = as_global(io.a_row) + S.xoff, a_col = as_global(io.a_col);
+    const gptr<double> a_val = as_global(io.a_val), x2 = as_global(io.x2);
+    switch (io.a_lanes) {
+      case 1: fused_spmv_rows<1>(P.nI, tid, a_row, a_col, a_val, x2, X); break;
+      case 2: fused_spmv_rows<2>(P.nI, tid, a_row, a_col, a_val, x2, X); break;
+      case 4: fused_spmv_rows<4>(P.nI, tid, a_row, a_col, a_val, x2, X); break;
+      default: fused_spmv_rows<8>(P.nI, tid, a_row, a_col, a_val, x2, X); break;
     }
   }
   __syncthreads();
@@ -2427,10 +2456,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
     __syncthreads();
     tick(ni > 128 ? 3 : 4);
   }
-  if (io.out == 0) {
+  if (OUT == 0) {
     for (int i = tid; i < P.nI; i += 256) xg[i] = X[i];
   } else {
-    for (int i = tid; i < P.nI; i += 256) io.user[io.perm[S.xoff + i]] = io.z[S.xoff + i] - X[i];
+    // x1 -= A11 \ y1 (k_axpby with -1, 1: z - X exactly) and the exit scatter (k_scatter)
+    const gptr<int32_t> perm = as_global(io.perm) + S.xoff;
+    const gptr<double> z = as_global(io.z) + S.xoff;
+    const gmptr<double> user = as_global_rw(io.user);
+    for (int i = tid; i < P.nI; i += 256) user[perm[i]] = z[i] - X[i];
   }
   if (PROF && tid == 0) {
     tp[5] = wall_clock64() - tstart;
@@ -2439,18 +2472,42 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
     prof[(int64_t)blockIdx.x * 8 + 7] = P.nI;
   }
 }
+// the plain solve, x in place
+template <bool PROF, class PT>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) k_interior_fused(const FusedSub* __restrict__ subs, const PlanD* __restrict__ plans,
+                                                         double* __restrict__ x, long long* __restrict__ prof) {
+  interior_fused_body<PROF, PT, 0, 0>(subs, plans, x, prof, FusedIO());
+}
+// the solve with a neighbouring vector pass in its load and / or store: <1, 0> and <2, 1> are the first and the second
+// interior solve of a single-vector ApplyInverse
+template <bool PROF, class PT, int IN, int OUT>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) k_interior_fused_io(const FusedSub* __restrict__ subs, const PlanD* __restrict__ plans,
+                                                            double* __restrict__ x, long long* __restrict__ prof, FusedIO io) {
+  interior_fused_body<PROF, PT, IN, OUT>(subs, plans, x, prof, io);
+}
 
+template <bool PROF, class PT>
+static void launch_fused_kernel(int32_t nsub, const FusedSub* subs, const PlanD* plans, size_t shm, double* x, long long* prof, const FusedIO& io) {
+  auto go = [&](auto kernel, auto... tail) {
+    if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL(kernel, dim3(nsub), dim3(256), shm, g_stream, subs, plans, x, prof, tail...);
+  };
+  if (io.in == 0 && io.out == 0) go(k_interior_fused<PROF, PT>);
+  else if (io.in == 1 && io.out == 0) go(k_interior_fused_io<PROF, PT, 1, 0>, io);
+  else if (io.in == 2 && io.out == 1) go(k_interior_fused_io<PROF, PT, 2, 1>, io);
+  else HYMLS_CHECK(false, -3, "fused interior solve: no kernel for this combination of FusedIO::in and FusedIO::out");
+  launch_check();
+}
 template <class PT>
 static void launch_fused(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, double* x, const FusedIO* iop) {
   const FusedIO io = iop ? *iop : FusedIO();
   if (nsub <= 0) return;
   const size_t shm = (size_t)lds_doubles * sizeof(double);
-  if (std::getenv("HYMLS_MI_FUSED_PROF")) {
+  static const bool phase_prof = std::getenv("HYMLS_MI_FUSED_PROF") != nullptr;
+  if (phase_prof) {
     // development aid: per-phase wall-clock ticks (100 MHz) of every workgroup, averaged, on stderr
     long long* dprof = (long long*)alloc((size_t)nsub * 8 * sizeof(long long));
-    if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_interior_fused<true, PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL((k_interior_fused<true, PT>), dim3(nsub), dim3(256), shm, g_stream, subs, plans, x, dprof, io);
-    launch_check();
+    launch_fused_kernel<true, PT>(nsub, subs, plans, shm, x, dprof, io);
     std::vector<long long> h((size_t)nsub * 8);
     d2h(h.data(), dprof, h.size() * sizeof(long long));
     free(dprof);
@@ -2461,9 +2518,7 @@ static void launch_fused(int32_t nsub, const FusedSub* subs, const PlanD* plans,
                  nsub, (tmax - tmin) / 100.0, sum[0] / nsub / 100, sum[1] / nsub / 100, sum[2] / nsub / 100, sum[3] / nsub / 100, sum[4] / nsub / 100, sum[5] / nsub / 100);
     return;
   }
-  if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_interior_fused<false, PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-  hipLaunchKernelGGL((k_interior_fused<false, PT>), dim3(nsub), dim3(256), shm, g_stream, subs, plans, x, (long long*)nullptr, io);
-  launch_check();
+  launch_fused_kernel<false, PT>(nsub, subs, plans, shm, x, nullptr, io);
 }
 void interior_solve_fused(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, double* x, const FusedIO* iop) {
   launch_fused<double>(nsub, subs, plans, lds_doubles, x, iop);

@@ -1063,6 +1063,18 @@ void LevelSolver::initialize() {
   d_a12_val_ = (double*)dev::alloc(std::max<size_t>(1, a12_col_.size()) * sizeof(double));
   d_a21_val_ = (double*)dev::alloc(std::max<size_t>(1, a21_col_.size()) * sizeof(double));
   d_flag_ = (int32_t*)dev::alloc(sizeof(int32_t));
+  // Fused vector passes of the single-vector apply (apply_inverse_mv): possible when the fused kernel solves every interior
+  // row, i.e. no class is left to the merged or the per-front route.  Development switch: HYMLS_MI_NO_FUSED_IO=1 keeps the
+  // separate gather / SpMV / axpby / scatter kernels.
+  {
+    int64_t covered = 0;
+    for (size_t c = 0; c < cls_.size(); c++)
+      if (cls_fused_[c]) covered += (int64_t)cls_[c]->lu.plan.nI * (int64_t)cls_[c]->lu.members.size();
+    fused_io_ = n1_ > 0 && covered == n1_ && merged_.nsubs == 0 && !std::getenv("HYMLS_MI_NO_FUSED_IO");
+    if (std::getenv("HYMLS_MI_VERBOSE"))
+      std::fprintf(stderr, "[hymls_mi] rank %d level %d: vector passes of the apply %s the interior solve (fused classes cover %lld of %d interior rows, A12 %.2f entries per row)\n",
+                   comm_->rank, level_, fused_io_ ? "fused into" : "separate from", (long long)covered, n1_, n1_ ? (double)a12_col_.size() / n1_ : 0.0);
+  }
   initialized_ = true;
 }
 
@@ -2327,16 +2339,18 @@ void LevelSolver::compute() {
 void LevelSolver::interior_solve(double* x1) { interior_solve_mv(x1, n1_ + ngi_, 1); }
 
 // x1 <- A11^{-1} x1 for nv columns (leading dimension ld): the factor panels are streamed once per group of columns
-void LevelSolver::interior_solve_mv(double* x1, int64_t ld, int nv) {
+// io (single vector, fused_io_ only): where the fused kernel takes its right-hand side from and where the result goes
+void LevelSolver::interior_solve_mv(double* x1, int64_t ld, int nv, const dev::FusedIO* io) {
   dev::Range range("MatrixBlock", level_ + 1, "ApplyInverse");
+  HYMLS_CHECK(io == nullptr || (fused_io_ && nv == 1), -3, "fused vector passes need the fused interior solve of one vector");
   if (n_fsubs_ > 0) {
 #ifdef HYMLS_MI_F32_PANELS
     if (fsubs_bits_ == 32) {
-      if (nv == 1) dev::interior_solve_fused_f32(n_fsubs_, d_fsubs_, d_fplans_, fused_lds_, x1);
+      if (nv == 1) dev::interior_solve_fused_f32(n_fsubs_, d_fsubs_, d_fplans_, fused_lds_, x1, io);
       else dev::interior_solve_fused_mv_f32(n_fsubs_, d_fsubs_, d_fplans_, fused_vec_lds_ + fused_front_lds_, fused_front_lds_, x1, ld, nv);
     } else
 #endif
-    if (nv == 1) dev::interior_solve_fused(n_fsubs_, d_fsubs_, d_fplans_, fused_lds_, x1);
+    if (nv == 1) dev::interior_solve_fused(n_fsubs_, d_fsubs_, d_fplans_, fused_lds_, x1, io);
     else dev::interior_solve_fused_mv(n_fsubs_, d_fsubs_, d_fplans_, fused_vec_lds_ + fused_front_lds_, fused_front_lds_, x1, ld, nv);
   }
   if (merged_.nsubs > 0) {
@@ -2405,7 +2419,12 @@ void LevelSolver::schur_apply(double* rhs2, int64_t ldr, double* x2, int64_t ldx
 void LevelSolver::apply_inverse(const double* b, double* x) { apply_inverse_mv(b, 0, x, 0, 1); }
 
 // Preconditioner::ApplyInverse (reference src/HYMLS_Preconditioner.cpp:930-1070) for nv right-hand sides; the two
-// interior solves, the separator blocks and the coarser levels read their factors once per group of up to NV_MAX columns
+// interior solves, the separator blocks and the coarser levels read their factors once per group of up to NV_MAX columns.
+// One vector on a level whose interiors are all solved by the fused kernel (fused_io_): the first launch gathers b1 itself,
+// the second one forms A12 x2 row by row, subtracts its solution from x1 and scatters into x, so the n1-sized gather,
+// SpMV, axpby and scatter kernels are not launched (same operations in the same order: same bits).  Several vectors
+// (k_interior_fused_mv) keep the separate kernels.  With the fusion phase 2 (phase_ms.spmv) holds the A21 product only;
+// the A12 product is timed with the second interior solve (phase 1).
 void LevelSolver::apply_inverse_mv(const double* b, int64_t ldb, double* x, int64_t ldx, int nv) {
   dev::Range range("Preconditioner", level_ + 1, "ApplyInverse");
   HYMLS_CHECK(next_ != nullptr || global_n2_ == 0, -1, "The preconditioner has not yet been computed.");
@@ -2413,13 +2432,20 @@ void LevelSolver::apply_inverse_mv(const double* b, int64_t ldb, double* x, int6
   const int64_t ldz = n1_ + ngi_ + n2_, ld1 = std::max(n1_, 1), ld2 = std::max(n2_ + ngs_, 1);
   double* z1 = d_z_;                    // per column: [x1 | x1 of the neighbours next to my separators | x2]
   double* z2 = d_z_ + n1_ + ngi_;
+  const bool fio = fused_io_ && nv == 1;
   if (profiling) dev::mark(0, true);
   for (int v = 0; v < nv; v++) {
-    dev::gather(n1_, d_inperm_, b + v * ldb, z1 + v * ldz);        // b1
+    if (!fio) dev::gather(n1_, d_inperm_, b + v * ldb, z1 + v * ldz);   // b1
     dev::gather(n2_, d_inperm_ + n1_, b + v * ldb, z2 + v * ldz);  // b2
   }
   if (profiling) dev::mark(1, true);
-  interior_solve_mv(z1, ldz, nv);                                  // x1 = A11 \ b1
+  if (fio) {
+    dev::FusedIO io;
+    io.in = 1; io.b = b; io.perm = d_inperm_;
+    interior_solve_mv(z1, ldz, 1, &io);                            // x1 = A11 \ b1, b1 read through the permutation
+  } else {
+    interior_solve_mv(z1, ldz, nv);                                // x1 = A11 \ b1
+  }
   if (profiling) { dev::mark(1, false); dev::mark(2, true); }
   for (int v = 0; v < nv; v++) {
     xch_int_.forward(z1 + v * ldz, z1 + v * ldz);                  // halo: interior layer of the neighbouring ranks
@@ -2427,7 +2453,21 @@ void LevelSolver::apply_inverse_mv(const double* b, int64_t ldb, double* x, int6
   }
   if (profiling) { dev::mark(2, false); dev::mark(3, true); }
   schur_apply(z2, ldz, d_t2_, ld2, nv);                            // x2
-  if (profiling) { dev::mark(3, false); dev::mark(2, true); }
+  if (profiling) dev::mark(3, false);
+  if (fio) {
+    xch_sep_.forward(d_t2_, d_t2_);                                // halo: separators owned by the neighbouring ranks
+    if (profiling) dev::mark(1, true);
+    dev::FusedIO io;
+    io.in = 2; io.a_row = d_a12_row_; io.a_col = d_a12_col_; io.a_val = d_a12_val_; io.x2 = d_t2_;
+    io.a_lanes = dev::spmv_lanes(n1_, (int64_t)a12_col_.size());   // the row sums of dev::spmv(n1_, A12, ...), bit for bit
+    io.out = 1; io.z = z1; io.user = x; io.perm = d_inperm_;
+    interior_solve_mv(d_t1_, ld1, 1, &io);                         // x[perm] = x1 - A11 \ (A12 x2); d_t1_ is not touched
+    if (profiling) dev::mark(1, false);
+    dev::scatter(n2_, d_inperm_ + n1_, d_t2_, x);
+    if (profiling) dev::mark(0, false);
+    return;
+  }
+  if (profiling) dev::mark(2, true);
   for (int v = 0; v < nv; v++) {
     xch_sep_.forward(d_t2_ + v * ld2, d_t2_ + v * ld2);            // halo: separators owned by the neighbouring ranks
     dev::spmv(n1_, d_a12_row_, d_a12_col_, d_a12_val_, d_t2_ + v * ld2, d_t1_ + v * ld1, 1.0, 0.0, (int64_t)a12_col_.size());  // y1 = A12 x2
@@ -2706,7 +2746,9 @@ void LevelSolver::add_stats(ApplyStats& st, bool as_coarse) const {
     for (auto& B : blocks_) sep += (8.0 * B.nb * B.nb + 4.0 * B.nb) * B.nblk;
   }
   const double N = (double)(n1_ + n2_);
-  vec = 8.0 * (4.0 * N + 7.0 * n1_ + 12.0 * n2_);
+  // n1-sized passes next to the gather / scatter of N: both solves in and out (4) and the axpby (3); with the vector passes
+  // fused into the solves (fused_io_) b1 and z1 are read once and z1 and x1 written once, which the 4 N cover already
+  vec = 8.0 * (4.0 * N + (fused_io_ ? 0.0 : 7.0) * n1_ + 12.0 * n2_);
   for (auto& cp : cls_) {
     st.flops_factor += (double)cp->lu.plan.flops_factor * (double)cp->lu.members.size();
     if (!direct_schur_) st.flops_transform += 4.0 * (double)cp->pat.nS * (double)cp->pat.nS * (double)cp->lu.members.size();

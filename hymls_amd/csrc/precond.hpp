@@ -260,7 +260,7 @@ class LevelSolver : public Operator {
   const Csr& assemble_reduced(ivec& row_gids, dvec* tvn);
   void schur_apply(double* rhs2, int64_t ldr, double* x2, int64_t ldx, int nv);
   void next_apply(const double* rhs, double* sol, int64_t ld, int nv);
-  void interior_solve_mv(double* x1, int64_t ld, int nv);
+  void interior_solve_mv(double* x1, int64_t ld, int nv, const dev::FusedIO* io = nullptr);
   void ensure_nvec(int nv);
   int nvec_alloc_ = 1;
   void build_handoff(const ivec& next_owned);
@@ -327,6 +327,9 @@ class LevelSolver : public Operator {
   dev::PlanD* d_fplans_ = nullptr;
   int32_t n_fsubs_ = 0, fused_lds_ = 0, fused_front_lds_ = 0, fused_vec_lds_ = 0;
   std::vector<char> cls_fused_;
+  // single-vector apply_inverse: entry gather, A12 product, x1 update and exit scatter of the interior part ride inside the
+  // two fused launches (dev::FusedIO).  Decided by initialize(): every interior row belongs to a fused class.
+  bool fused_io_ = false;
   int factor_bits_ = 64;   // wanted (set_factor_bits)
   int fsubs_bits_ = 64;    // what the slabs and d_fsubs_ hold since the last compute()
   void prepare_factor_storage();   // start of compute(): slabs and d_fsubs_ for factor_bits_
