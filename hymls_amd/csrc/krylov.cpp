@@ -8,6 +8,11 @@
 // One GMRES iteration on one GPU: ApplyInverse, K x, the three orthogonalisation passes with their device reductions
 // (krylov_hip.hip), the normalisation of the new basis column, and one device-to-host copy of (h1 + h2, ||w||) -- the
 // single synchronisation of the iteration.  Sharded handles add a host all-sum (rank order) after every pass.
+//
+// FP32 basis storage (hymls_mi_solver_set_basis_storage(s, 32), compressed-basis GMRES): the basis columns are floats,
+// every other vector and every sum stays FP64.  Column k is widened into t for ApplyInverse and K x, the three passes
+// orthogonalise the FP64 w in place against the float columns, and w / ||w|| is formed in FP64 and rounded once into
+// column k + 1.  A cycle ends early at KRY_F32_CYCLE_THETA, and only an explicitly computed residual ends the solve.
 #include "../../include/hymls_mi_solver.h"
 #include "capi_internal.hpp"
 #include "krylov.hpp"
@@ -16,16 +21,29 @@
 
 using namespace hymls;
 
+// FP32 basis: a cycle ends as soon as the Givens estimate has fallen to theta times the residual the cycle started from.
+// Inside one cycle a float basis cannot reduce the residual by much more than 1e-7: beyond that the estimate keeps falling
+// while the true residual stalls.  Iterations to the tolerance on the numpy oracle (CGS2 GMRES(250), right preconditioned;
+// FP64 basis -> FP32 basis with theta = 1e-5), tolerances 1e-8 / 1e-10 / 1e-12:
+//   Stokes-C 16^3, Skew, sx 8, 1 level:   89 -> 95,   109 -> 115,  135 -> 141   (without the rule at 1e-8: 116, at 1e-10: 159)
+//   Stokes-C 16^3, Skew, sx 4, 2 levels:  89 -> 95,   110 -> 116,  139 -> 143   (without the rule at 1e-12: 284)
+//   Laplace 32^3, sx 4, 2 levels:         27 -> 28,   34 -> 34,    40 -> 42
+// theta = 1e-4 or 1e-6 stays within 3 iterations of these.
+static constexpr double KRY_F32_CYCLE_THETA = 1e-5;
+
 struct hymls_mi_solver {
   hymls_mi_t* h = nullptr;
   hymls_mi_solver_params p{};
   std::string err;
   int its = 0;
   double achieved = std::numeric_limits<double>::quiet_NaN();
+  int restarts = 0;                // Arnoldi cycles of the last column after its first one
+  int basis_bits = 64;             // hymls_mi_solver_set_basis_storage: storage of the GMRES basis from the next solve on
   // device memory, allocated at the first solve and kept (grown when the row count or the restart length grows)
   int64_t n = 0, ld = 0;           // rows of this rank, leading dimension of the basis (multiple of 16 doubles)
   int m_alloc = 0;                 // basis columns allocated
-  double* V = nullptr;             // [(m + 1) * ld]
+  int bits_alloc = 64;             // storage the basis was allocated for
+  double* V = nullptr;             // [(m + 1) * ld]; FP32 storage: the same allocation holds float[(m + 1) * ld]
   double* vec = nullptr;           // 7 vectors of ld: x, r, w, t, p, prev, staged b
   double* work = nullptr;          // reduction scratch (dev::KryWork)
   dev::KryWork ws{};
@@ -64,10 +82,12 @@ struct Run {
   double norm(const double* a) { return std::sqrt(dot(a, a)); }
 
   // w <- (I - V V^T)^2 w over the k columns of V, written to dst; hk[0..k) = h1 + h2, hk[k] = ||dst||
-  void orthogonalize(int k, const double* Vb, int64_t ldv, double* wv, double* dst, double* hk) {
+  template <class BT>
+  void orthogonalize(int k, const BT* Vb, int64_t ldv, double* wv, double* dst, double* hk) {
     orthogonalize_step(s->ws, comm, dist, n, k, Vb, ldv, wv, dst, hk);
   }
-  static void orthogonalize_step(const dev::KryWork& ws, const Comm* comm, bool dist, int64_t n, int k, const double* Vb,
+  template <class BT>   // BT: element type of the basis (float only under HYMLS_MI_F32_BASIS)
+  static void orthogonalize_step(const dev::KryWork& ws, const Comm* comm, bool dist, int64_t n, int k, const BT* Vb,
                                  int64_t ldv, double* wv, double* dst, double* hk) {
     dev::kry_pass_a(n, k, Vb, ldv, wv, ws);
     std::vector<double> h1, h2;
@@ -96,17 +116,23 @@ struct Run {
     }
   }
 
-  // restarted GMRES (solver.py: Solver._gmres); x holds the start vector
-  void gmres(const double* b, int& its, double& rel) {
+  // restarted GMRES (solver.py: Solver._gmres); x holds the start vector.  BT = double: the FP64 basis.  BT = float:
+  // the FP32 basis, where the Givens estimate only ends a cycle (at the tolerance, or at KRY_F32_CYCLE_THETA times the
+  // cycle's first residual) and the explicit residual at the top of the next cycle decides; rel is then always explicit
+  template <class BT>
+  void gmres(const double* b, int& its, double& rel, int& restarts) {
+    constexpr bool F32 = sizeof(BT) == 4;
     const hymls_mi_solver_params& P = s->p;
     const int m = std::min(P.num_blocks, P.max_iters);
     const bool right = P.right != 0;
-    double* V = s->V;
+    BT* V = (BT*)s->V;
     its = 0;
+    restarts = 0;
     rel = std::numeric_limits<double>::infinity();
     double beta0 = -1.0;
     std::vector<double> H, cs, sn, g, hk(dev::KRY_KMAX + 2), y;
-    for (int cycle = 0; cycle <= P.max_restarts; cycle++) {
+    // FP32 basis: the loop is left only at its top, after an explicit residual (one more than the cycles allowed)
+    for (int cycle = 0; cycle <= P.max_restarts + (F32 ? 1 : 0); cycle++) {
       if (its > 0 || dot(x, x) > 0.0) {
         matvec(x, t);
         mark(3, true); dev::kry_sub(n, b, t, r); mark(3, false);
@@ -119,21 +145,18 @@ struct Run {
       if (beta0 < 0) beta0 = beta;
       if (beta0 == 0.0) { rel = 0.0; return; }
       rel = beta / beta0;
-      if (rel <= P.tol || its >= P.max_iters) break;
-      mark(3, true); dev::kry_div(n, rr, beta, V); mark(3, false);
+      if (rel <= P.tol || its >= P.max_iters || cycle > P.max_restarts) break;
+      if (cycle > 0) restarts++;
+      mark(3, true); first_column(rr, beta, V); mark(3, false);
       H.assign((size_t)(m + 1) * m, 0.0);   // H[i + (m + 1) * k]
       cs.assign(m, 0.0); sn.assign(m, 0.0); g.assign(m + 1, 0.0);
       g[0] = beta;
       auto Hk = [&](int i, int k) -> double& { return H[(size_t)i + (size_t)(m + 1) * k]; };
       int k_used = 0;
       for (int k = 0; k < m; k++) {
-        const double* vk = V + (int64_t)k * ld;
-        if (right) { prec(vk, t); matvec(t, w); }
-        else { matvec(vk, t); prec(t, w); }
+        arnoldi_product(V + (int64_t)k * ld, right);
         mark(3, true);
-        double* vn = V + (int64_t)(k + 1) * ld;
-        orthogonalize(k + 1, V, ld, w, vn, hk.data());
-        dev::kry_scale_by(n, vn, s->ws.out + k + 1);   // V[k + 1] = w / ||w|| where ||w|| > 0
+        new_column(k, V, hk.data());
         if (!dist) dev::d2h(hk.data(), s->ws.out, (k + 2) * sizeof(double));
         mark(3, false);
         for (int i = 0; i <= k + 1; i++) Hk(i, k) = hk[i];
@@ -149,6 +172,7 @@ struct Run {
         its++; k_used = k + 1;
         rel = std::fabs(g[k + 1]) / beta0;
         if (rel <= P.tol || its >= P.max_iters) break;
+        if (F32 && std::fabs(g[k + 1]) <= KRY_F32_CYCLE_THETA * beta) break;
       }
       // y = H(0:k_used, 0:k_used) \ g, upper triangular
       y.assign(k_used, 0.0);
@@ -165,9 +189,33 @@ struct Run {
       } else {
         mark(3, true); dev::kry_update(n, k_used, V, ld, s->ws.h1, x); mark(3, false);
       }
-      if (rel <= P.tol || its >= P.max_iters) break;
+      if (!F32 && (rel <= P.tol || its >= P.max_iters)) break;
     }
   }
+
+  // the pieces of an Arnoldi step that differ between the two basis storages
+  void first_column(const double* rr, double beta, double* V) { dev::kry_div(n, rr, beta, V); }
+  void arnoldi_product(const double* vk, bool right) {
+    if (right) { prec(vk, t); matvec(t, w); }
+    else { matvec(vk, t); prec(t, w); }
+  }
+  void new_column(int k, double* V, double* hk) {
+    double* vn = V + (int64_t)(k + 1) * ld;
+    orthogonalize(k + 1, V, ld, w, vn, hk);
+    dev::kry_scale_by(n, vn, s->ws.out + k + 1);   // V[k + 1] = w / ||w|| where ||w|| > 0
+  }
+#ifdef HYMLS_MI_F32_BASIS
+  void first_column(const double* rr, double beta, float* V) { dev::kry_round_div(n, rr, beta, V); }
+  void arnoldi_product(const float* vk, bool right) {
+    mark(3, true); dev::kry_widen(n, vk, t); mark(3, false);   // p is free in GMRES: the second FP64 vector of the product
+    if (right) { prec(t, p); matvec(p, w); }
+    else { matvec(t, p); prec(p, w); }
+  }
+  void new_column(int k, float* V, double* hk) {
+    orthogonalize(k + 1, V, ld, w, w, hk);
+    dev::kry_round_scale_by(n, w, s->ws.out + k + 1, V + (int64_t)(k + 1) * ld);   // (float)(w / ||w||)
+  }
+#endif
 
   // preconditioned CG (solver.py: Solver._cg)
   void cg(const double* b, int& its, double& rel) {
@@ -306,12 +354,14 @@ int hymls_mi_solver_solve(hymls_mi_solver_t* s, const double* B, int64_t ldb, do
     s->ws.h2 = s->ws.h1 + dev::KRY_KMAX;
     s->ws.out = s->ws.h2 + dev::KRY_KMAX;
   }
-  if (gm && m > s->m_alloc) {
+  if (gm && (m > s->m_alloc || s->basis_bits != s->bits_alloc)) {
     dev::sync();
     dev::free(s->V);
     s->V = nullptr;
-    s->V = (double*)dev::alloc((size_t)(m + 1) * s->ld * sizeof(double));
+    s->m_alloc = 0;
+    s->V = (double*)dev::alloc((size_t)(m + 1) * s->ld * (s->basis_bits / 8));
     s->m_alloc = m;
+    s->bits_alloc = s->basis_bits;
   }
   Run R{s, L, hv_.comm, n, s->ld, hv_.comm->distributed()};
   double* v = s->vec;
@@ -333,11 +383,16 @@ int hymls_mi_solver_solve(hymls_mi_solver_t* s, const double* B, int64_t ldb, do
     else if (s->p.initial_vector == 2 && s->have_prev) dev::d2d(R.x, R.prev, n * sizeof(double));
     else dev::zero(R.x, n * sizeof(double));
     R.mark(0, true);
-    int its = 0;
+    int its = 0, restarts = 0;
     double rel = 0;
-    if (gm) R.gmres(b, its, rel); else R.cg(b, its, rel);
+    if (!gm) R.cg(b, its, rel);
+#ifdef HYMLS_MI_F32_BASIS
+    else if (s->basis_bits == 32) R.gmres<float>(b, its, rel, restarts);
+#endif
+    else R.gmres<double>(b, its, rel, restarts);
     R.mark(0, false);
     s->its = its;
+    s->restarts = restarts;
     s->achieved = rel;
     dev::d2d(R.prev, R.x, n * sizeof(double));
     s->have_prev = true;
@@ -358,6 +413,21 @@ int hymls_mi_solver_solve(hymls_mi_solver_t* s, const double* B, int64_t ldb, do
 
 int hymls_mi_solver_num_iters(const hymls_mi_solver_t* s) { return s ? s->its : 0; }
 double hymls_mi_solver_achieved_tol(const hymls_mi_solver_t* s) { return s ? s->achieved : std::numeric_limits<double>::quiet_NaN(); }
+
+int hymls_mi_solver_num_restarts(const hymls_mi_solver_t* s) { return s ? s->restarts : 0; }
+
+int hymls_mi_solver_set_basis_storage(hymls_mi_solver_t* s, int bits) {
+  if (!s) return -2;
+  try {
+    HYMLS_CHECK(bits == 64 || bits == 32, -2, "basis storage: 64 or 32 bits per basis entry");
+#ifndef HYMLS_MI_F32_BASIS
+    HYMLS_CHECK(bits == 64, -99, "this build has no FP32 basis kernels (the test-only simulator without them)");
+#endif
+    s->basis_bits = bits;
+  } catch (const hymls::Error& e) { s->err = e.what(); return e.code; }
+  return 0;
+}
+int hymls_mi_solver_basis_storage(const hymls_mi_solver_t* s) { return s ? s->basis_bits : 0; }
 
 int hymls_mi_solver_set_profiling(hymls_mi_solver_t* s, int on) {
   if (!s) return -2;
@@ -400,6 +470,41 @@ int hymls_mi_orthogonalize(hymls_mi_t* h, int64_t n, int32_t k, const double* V,
     dev::free(work);
     std::copy(hk.begin(), hk.begin() + k, hcoef);
     *wnorm = hk[k];
+  } catch (const hymls::Error& e) { *hv.err = e.what(); return e.code; }
+  catch (const std::exception& e) { *hv.err = e.what(); return -3; }
+  return 0;
+}
+
+int hymls_mi_orthogonalize_f32(hymls_mi_t* h, int64_t n, int32_t k, const float* V, int64_t ldv, double* w, float* vnext,
+                               double* hcoef, double* wnorm) {
+  if (!h) return -2;
+  HandleView hv = handle_view(h);
+  try {
+#ifndef HYMLS_MI_F32_BASIS
+    (void)n; (void)k; (void)V; (void)ldv; (void)w; (void)vnext; (void)hcoef; (void)wnorm;
+    throw hymls::Error(-99, "this build has no FP32 basis kernels (the test-only simulator without them)");
+#else
+    dev::bind(hv.ctx);
+    HYMLS_CHECK(n >= 1 && k >= 1 && k <= dev::KRY_KMAX && ldv >= n && V && w && hcoef && wnorm, -2,
+                "orthogonalize_f32: need n >= 1, 1 <= k <= 256, ldv >= n and non-null arrays");
+    double* work = (double*)dev::alloc(dev::kry_work_doubles() * sizeof(double));
+    dev::KryWork ws;
+    ws.part = work;
+    ws.h1 = work + (size_t)dev::KRY_MAXGRID * dev::KRY_KMAX;
+    ws.h2 = ws.h1 + dev::KRY_KMAX;
+    ws.out = ws.h2 + dev::KRY_KMAX;
+    std::vector<double> hk(k + 1);
+    const bool dist = hv.comm->distributed();
+    try {
+      Run::orthogonalize_step(ws, hv.comm, dist, n, k, V, ldv, w, w, hk.data());
+      if (vnext) dev::kry_round_scale_by(n, w, ws.out + k, vnext);
+      if (!dist) dev::d2h(hk.data(), ws.out, (k + 1) * sizeof(double));
+      else dev::sync();
+    } catch (...) { dev::free(work); throw; }
+    dev::free(work);
+    std::copy(hk.begin(), hk.begin() + k, hcoef);
+    *wnorm = hk[k];
+#endif
   } catch (const hymls::Error& e) { *hv.err = e.what(); return e.code; }
   catch (const std::exception& e) { *hv.err = e.what(); return -3; }
   return 0;

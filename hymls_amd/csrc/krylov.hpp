@@ -26,6 +26,18 @@ inline int kry_tile_grid(int64_t n, int32_t k) {
   const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(8, (int64_t)(160 * 1024) / (int64_t)kry_tile_lds(k)));
   return (int)std::max<int64_t>(1, std::min<int64_t>((n + KRY_TILE - 1) / KRY_TILE, 256 * per_cu));
 }
+// FP32 basis ("MI Basis Storage" = single): the tile holds floats, the vectors and partial sums next to it stay FP64.
+// Column stride 65 floats: a wave stages or reads 64 consecutive floats of one column (32 consecutive dwords per
+// 32-lane half: 32 distinct banks), and in the dot loop lane t reads dword 65 t + r, bank (t + r) mod 32: the 32 lanes
+// of a half hit 32 distinct banks.  Both access kinds are 4-byte LDS operations, banked modulo 32.
+constexpr int KRY_LD_TILE_F32 = KRY_TILE + 1;
+inline size_t kry_tile_lds_f32(int32_t k) {
+  return (size_t)(KRY_TILE + KRY_KMAX + 4 * KRY_TILE) * sizeof(double) + (size_t)KRY_LD_TILE_F32 * k * sizeof(float);
+}
+inline int kry_tile_grid_f32(int64_t n, int32_t k) {
+  const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(8, (int64_t)(160 * 1024) / (int64_t)kry_tile_lds_f32(k)));
+  return (int)std::max<int64_t>(1, std::min<int64_t>((n + KRY_TILE - 1) / KRY_TILE, 256 * per_cu));
+}
 inline int kry_row_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, KRY_MAXGRID)); }
 
 // scratch of the reductions, device memory (krylov.cpp allocates it with kry_work_doubles() doubles)
@@ -59,6 +71,20 @@ void kry_dot(int64_t n, const double* x, const double* y, const KryWork& ws);
 void kry_cg_xr(int64_t n, double alpha, const double* p, const double* q, double* x, double* r, const KryWork& ws);
 // CG: p <- z + beta p
 void kry_cg_p(int64_t n, double beta, const double* z, double* p);
+
+// ---- FP32 basis: the same passes over float columns.  w, h1, h2, every partial and every sum stay FP64; a basis entry
+// is widened when it is read.  Implemented by krylov_hip.hip and by the test-only tests/krylov_f32_sim; krylov.cpp
+// refers to them only under HYMLS_MI_F32_BASIS, because tests/krylov_sim has none.
+void kry_pass_a(int64_t n, int32_t k, const float* V, int64_t ldv, const double* w, const KryWork& ws);
+void kry_pass_b(int64_t n, int32_t k, const float* V, int64_t ldv, double* w, const KryWork& ws);
+void kry_pass_c(int64_t n, int32_t k, const float* V, int64_t ldv, const double* w, double* dst, const KryWork& ws);
+void kry_update(int64_t n, int32_t k, const float* V, int64_t ldv, const double* y, double* x);
+// t <- (double) v: the FP64 copy of a basis column that ApplyInverse and K x read
+void kry_widen(int64_t n, const float* v, double* t);
+// y <- (float)(x / s): the first column of a cycle
+void kry_round_div(int64_t n, const double* x, double s, float* y);
+// y <- (float)(x / *d) where *d > 0, else (float) x (device scalar): the new column, normalised in FP64 and rounded once
+void kry_round_scale_by(int64_t n, const double* x, const double* d, float* y);
 
 // phase timing of a solve: events recorded on the stream (the simulator takes host clock readings)
 struct KryTimer;

@@ -12,6 +12,12 @@
 //   k_kry_reduce*       stage two of every reduction: the partials of one column summed by one workgroup in a fixed
 //                       tree, on the device, so h1 feeds pass B and h2 pass C without a host round trip
 // plus the vector passes of GMRES and CG.  No atomics anywhere: every result is bitwise reproducible.
+//
+// k_kry_tile and k_kry_rows take the element type of the basis.  With float ("MI Basis Storage" = single) a basis entry
+// is widened when it is used and every product and sum stays FP64; the tile in LDS holds floats (column stride 65
+// floats, krylov.hpp: kry_tile_lds_f32), which is what bounds the workgroups per CU of passes A and B.  Three small
+// kernels go with it: k_kry_widen (the FP64 copy of a column), k_kry_round_div and k_kry_round_scale_by (a quotient
+// formed in FP64 and rounded once into a float column).
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <string>
@@ -40,14 +46,17 @@ __device__ inline void block_sum256(double* red) {
   __syncthreads();
 }
 
-// ---- passes A and B
-template <bool UPD>
-__global__ void __launch_bounds__(256) k_kry_tile(int64_t n, int k, const double* __restrict__ V, int64_t ldv, double* w,
+// ---- passes A and B; BT: the element type of the basis (double, or float with "MI Basis Storage" = single).  Every product
+// and sum is FP64: a float entry is widened when it leaves LDS
+template <bool UPD, class BT>
+__global__ void __launch_bounds__(256) k_kry_tile(int64_t n, int k, const BT* __restrict__ V, int64_t ldv, double* w,
                                                   const double* __restrict__ h1, double* __restrict__ part) {
   extern __shared__ double sm[];
-  constexpr int T = KRY_TILE, LT = KRY_LD_TILE;
-  double* Vs = sm;                   // [k][LT]: column j of the tile at Vs[j * LT]
-  double* ws = Vs + (size_t)LT * k;  // [T]
+  constexpr bool F32 = sizeof(BT) == 4;
+  constexpr int T = KRY_TILE, LT = F32 ? KRY_LD_TILE_F32 : KRY_LD_TILE;
+  // FP64 basis: tile, ws, hs, red.  FP32 basis: the FP64 arrays first, so that they stay 8-byte aligned for every k
+  BT* Vs = F32 ? (BT*)(sm + T + KRY_KMAX + 4 * T) : (BT*)sm;   // [k][LT]: column j of the tile at Vs[j * LT]
+  double* ws = F32 ? sm : sm + (size_t)LT * k;                 // [T]
   double* hs = ws + T;               // [KRY_KMAX]
   double* red = hs + KRY_KMAX;       // [4][T]
   const int t = threadIdx.x;
@@ -61,7 +70,7 @@ __global__ void __launch_bounds__(256) k_kry_tile(int64_t n, int k, const double
     __syncthreads();   // the previous tile is no longer read
     for (int e = t; e < T * k; e += 256) {
       const int r = e & (T - 1), j = e / T;
-      Vs[j * LT + r] = r < rows ? V[(int64_t)j * ldv + r0 + r] : 0.0;
+      Vs[j * LT + r] = r < rows ? V[(int64_t)j * ldv + r0 + r] : (BT)0;
     }
     if (t < T) ws[t] = t < rows ? w[r0 + t] : 0.0;
     __syncthreads();
@@ -69,7 +78,7 @@ __global__ void __launch_bounds__(256) k_kry_tile(int64_t n, int k, const double
       // w - V h1 for the tile: wave q adds the columns j = q mod 4 of row r = lane, the four sums are added in wave order
       const int r = t & (T - 1), q = t / T;
       double s = 0.0;
-      for (int j = q; j < k; j += 4) s += Vs[j * LT + r] * hs[j];
+      for (int j = q; j < k; j += 4) s += (double)Vs[j * LT + r] * hs[j];
       red[q * T + r] = s;
       __syncthreads();
       if (t < T) {
@@ -80,17 +89,17 @@ __global__ void __launch_bounds__(256) k_kry_tile(int64_t n, int k, const double
       __syncthreads();
     }
     if (t < k) {
-      const double* c = Vs + t * LT;
+      const BT* c = Vs + t * LT;
 #pragma unroll 8
-      for (int r = 0; r < T; r++) acc += c[r] * ws[r];
+      for (int r = 0; r < T; r++) acc += (double)c[r] * ws[r];
     }
   }
   if (t < k) part[(int64_t)blockIdx.x * k + t] = acc;
 }
 
 // ---- pass C (NORM) and the solution update
-template <bool NORM>
-__global__ void __launch_bounds__(256) k_kry_rows(int64_t n, int k, const double* __restrict__ V, int64_t ldv,
+template <bool NORM, class BT>
+__global__ void __launch_bounds__(256) k_kry_rows(int64_t n, int k, const BT* __restrict__ V, int64_t ldv,
                                                   const double* __restrict__ h, const double* w, double* dst,
                                                   double* __restrict__ part) {
   __shared__ double hs[KRY_KMAX];
@@ -100,10 +109,10 @@ __global__ void __launch_bounds__(256) k_kry_rows(int64_t n, int k, const double
   __syncthreads();
   double ss = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + t; i < n; i += (int64_t)gridDim.x * 256) {
-    const double* v = V + i;
+    const BT* v = V + i;
     double s = 0.0;
 #pragma unroll 8
-    for (int j = 0; j < k; j++) s += v[(int64_t)j * ldv] * hs[j];
+    for (int j = 0; j < k; j++) s += (double)v[(int64_t)j * ldv] * hs[j];
     if (NORM) {
       const double x = w[i] - s;
       dst[i] = x;
@@ -153,6 +162,20 @@ __global__ void __launch_bounds__(256) k_kry_scale_by(int64_t n, double* x, cons
 __global__ void __launch_bounds__(256) k_kry_div(int64_t n, const double* x, double s, double* y) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = x[i] / s;
 }
+// FP32 basis: the widening copy of a column, and the two stores that round a quotient formed in FP64 once
+__global__ void __launch_bounds__(256) k_kry_widen(int64_t n, const float* __restrict__ v, double* __restrict__ t) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) t[i] = (double)v[i];
+}
+__global__ void __launch_bounds__(256) k_kry_round_div(int64_t n, const double* __restrict__ x, double s, float* __restrict__ y) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = (float)(x[i] / s);
+}
+__global__ void __launch_bounds__(256) k_kry_round_scale_by(int64_t n, const double* __restrict__ x, const double* d,
+                                                            float* __restrict__ y) {
+  const double s = *d;
+  const bool pos = s > 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    y[i] = (float)(pos ? x[i] / s : x[i]);
+}
 __global__ void __launch_bounds__(256) k_kry_sub(int64_t n, const double* b, const double* y, double* r) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) r[i] = b[i] - y[i];
 }
@@ -189,24 +212,41 @@ __global__ void __launch_bounds__(256) k_kry_cg_p(int64_t n, double beta, const 
 
 static inline void kcheck() { KRY_CHECK(hipGetLastError()); }
 
-template <bool UPD>
-static void tile_pass(int64_t n, int32_t k, const double* V, int64_t ldv, double* w, const KryWork& ws) {
+template <bool UPD, class BT>
+static void tile_pass(int64_t n, int32_t k, const BT* V, int64_t ldv, double* w, const KryWork& ws) {
   if (k < 1 || k > KRY_KMAX) throw Error(-2, "orthogonalisation: 1 <= k <= 256 columns");
-  const int nb = kry_tile_grid(n, k);
-  const size_t shm = kry_tile_lds(k);
-  static thread_local int attr_device = -1;   // the attribute is per device
+  constexpr bool F32 = sizeof(BT) == 4;
+  const int nb = F32 ? kry_tile_grid_f32(n, k) : kry_tile_grid(n, k);
+  const size_t shm = F32 ? kry_tile_lds_f32(k) : kry_tile_lds(k);
+  static thread_local int attr_device = -1;   // the attribute is per device (and per basis type: one variable each)
   int devno = 0;
   KRY_CHECK(hipGetDevice(&devno));
   if (attr_device != devno) {
-    const int most = (int)kry_tile_lds(KRY_KMAX);
-    KRY_CHECK(hipFuncSetAttribute((const void*)k_kry_tile<false>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-    KRY_CHECK(hipFuncSetAttribute((const void*)k_kry_tile<true>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+    const int most = (int)(F32 ? kry_tile_lds_f32(KRY_KMAX) : kry_tile_lds(KRY_KMAX));
+    KRY_CHECK(hipFuncSetAttribute((const void*)k_kry_tile<false, BT>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+    KRY_CHECK(hipFuncSetAttribute((const void*)k_kry_tile<true, BT>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
     attr_device = devno;
   }
-  hipLaunchKernelGGL(k_kry_tile<UPD>, dim3(nb), dim3(256), shm, kstream(), n, k, V, ldv, w, ws.h1, ws.part);
+  hipLaunchKernelGGL((k_kry_tile<UPD, BT>), dim3(nb), dim3(256), shm, kstream(), n, k, V, ldv, w, ws.h1, ws.part);
   kcheck();
   if (UPD) hipLaunchKernelGGL(k_kry_reduce, dim3(k), dim3(256), 0, kstream(), ws.part, nb, k, ws.h2, ws.h1, ws.out);
   else hipLaunchKernelGGL(k_kry_reduce, dim3(k), dim3(256), 0, kstream(), ws.part, nb, k, ws.h1, nullptr, nullptr);
+  kcheck();
+}
+template <class BT>
+static void row_pass_c(int64_t n, int32_t k, const BT* V, int64_t ldv, const double* w, double* dst, const KryWork& ws) {
+  if (k < 1 || k > KRY_KMAX) throw Error(-2, "orthogonalisation: 1 <= k <= 256 columns");
+  const int nb = kry_row_grid(n);
+  hipLaunchKernelGGL((k_kry_rows<true, BT>), dim3(nb), dim3(256), 0, kstream(), n, k, V, ldv, ws.h2, w, dst, ws.part);
+  kcheck();
+  hipLaunchKernelGGL(k_kry_reduce_norm, dim3(1), dim3(256), 0, kstream(), ws.part, nb, ws.out + k);
+  kcheck();
+}
+template <class BT>
+static void row_update(int64_t n, int32_t k, const BT* V, int64_t ldv, const double* y, double* x) {
+  if (k < 1) return;
+  if (k > KRY_KMAX) throw Error(-2, "basis update: at most 256 columns");
+  hipLaunchKernelGGL((k_kry_rows<false, BT>), dim3(kry_row_grid(n)), dim3(256), 0, kstream(), n, k, V, ldv, y, x, x, nullptr);
   kcheck();
 }
 
@@ -217,17 +257,33 @@ void kry_pass_b(int64_t n, int32_t k, const double* V, int64_t ldv, double* w, c
   tile_pass<true>(n, k, V, ldv, w, ws);
 }
 void kry_pass_c(int64_t n, int32_t k, const double* V, int64_t ldv, const double* w, double* dst, const KryWork& ws) {
-  if (k < 1 || k > KRY_KMAX) throw Error(-2, "orthogonalisation: 1 <= k <= 256 columns");
-  const int nb = kry_row_grid(n);
-  hipLaunchKernelGGL(k_kry_rows<true>, dim3(nb), dim3(256), 0, kstream(), n, k, V, ldv, ws.h2, w, dst, ws.part);
-  kcheck();
-  hipLaunchKernelGGL(k_kry_reduce_norm, dim3(1), dim3(256), 0, kstream(), ws.part, nb, ws.out + k);
-  kcheck();
+  row_pass_c(n, k, V, ldv, w, dst, ws);
 }
 void kry_update(int64_t n, int32_t k, const double* V, int64_t ldv, const double* y, double* x) {
-  if (k < 1) return;
-  if (k > KRY_KMAX) throw Error(-2, "basis update: at most 256 columns");
-  hipLaunchKernelGGL(k_kry_rows<false>, dim3(kry_row_grid(n)), dim3(256), 0, kstream(), n, k, V, ldv, y, x, x, nullptr);
+  row_update(n, k, V, ldv, y, x);
+}
+void kry_pass_a(int64_t n, int32_t k, const float* V, int64_t ldv, const double* w, const KryWork& ws) {
+  tile_pass<false>(n, k, V, ldv, const_cast<double*>(w), ws);
+}
+void kry_pass_b(int64_t n, int32_t k, const float* V, int64_t ldv, double* w, const KryWork& ws) {
+  tile_pass<true>(n, k, V, ldv, w, ws);
+}
+void kry_pass_c(int64_t n, int32_t k, const float* V, int64_t ldv, const double* w, double* dst, const KryWork& ws) {
+  row_pass_c(n, k, V, ldv, w, dst, ws);
+}
+void kry_update(int64_t n, int32_t k, const float* V, int64_t ldv, const double* y, double* x) {
+  row_update(n, k, V, ldv, y, x);
+}
+void kry_widen(int64_t n, const float* v, double* t) {
+  hipLaunchKernelGGL(k_kry_widen, dim3(vec_grid(n)), dim3(256), 0, kstream(), n, v, t);
+  kcheck();
+}
+void kry_round_div(int64_t n, const double* x, double s, float* y) {
+  hipLaunchKernelGGL(k_kry_round_div, dim3(vec_grid(n)), dim3(256), 0, kstream(), n, x, s, y);
+  kcheck();
+}
+void kry_round_scale_by(int64_t n, const double* x, const double* d, float* y) {
+  hipLaunchKernelGGL(k_kry_round_scale_by, dim3(vec_grid(n)), dim3(256), 0, kstream(), n, x, d, y);
   kcheck();
 }
 void kry_scale_by(int64_t n, double* x, const double* d) {

@@ -14,6 +14,7 @@ from .api import HymlsError
 
 METHODS = {"GMRES": 0, "CG": 1}
 STARTS = {"Zero": 0, "Random": 1, "Previous": 2}
+BASIS_STORAGE = {"double": 64, "single": 32}    # "MI Basis Storage" (hymls_mi_solver_set_basis_storage)
 
 
 class _SolverParams(C.Structure):
@@ -33,6 +34,11 @@ _SIG = {
     "hymls_mi_solver_seconds": (C.c_double, [C.c_void_p, C.c_int]),
     "hymls_mi_orthogonalize": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                          C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "hymls_mi_solver_num_restarts": (C.c_int, [C.c_void_p]),
+    "hymls_mi_solver_set_basis_storage": (C.c_int, [C.c_void_p, C.c_int]),
+    "hymls_mi_solver_basis_storage": (C.c_int, [C.c_void_p]),
+    "hymls_mi_orthogonalize_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                             C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "hymls_mi_solver_last_error": (C.c_char_p, [C.c_void_p]),
     "hymls_mi_solver_destroy": (None, [C.c_void_p]),
 }
@@ -72,6 +78,14 @@ def solver_params(params):
     return p
 
 
+def basis_bits(params):
+    """"MI Basis Storage" of the Solver sublist ("double", the default, or "single") as the bits of a basis entry"""
+    storage = params.get("Solver", params).get("MI Basis Storage", "double")
+    if storage not in BASIS_STORAGE:
+        raise ValueError("MI Basis Storage must be double or single")
+    return BASIS_STORAGE[storage]
+
+
 class NativeSolver:
     """K x = b with the library's own Krylov loop; P: a computed hymls_amd.Preconditioner (sharded or not)."""
 
@@ -80,7 +94,10 @@ class NativeSolver:
         self._lib = bind_solver(P._lib)
         self._s = C.c_void_p()
         self._params = solver_params(params or {})
+        bits = basis_bits(params or {})
         ierr = self._lib.hymls_mi_solver_create(C.byref(self._s), P._h, C.byref(self._params))
+        if not ierr:
+            ierr = self._lib.hymls_mi_solver_set_basis_storage(self._s, bits)
         if ierr:
             msg = self._lib.hymls_mi_solver_last_error(self._s).decode() if self._s else "create failed"
             self.close()
@@ -94,8 +111,10 @@ class NativeSolver:
     def setParameterList(self, params):
         """replaces every parameter; a "Previous" start still uses the last solution"""
         p = solver_params(params)
+        bits = basis_bits(params)
         self._check(self._lib.hymls_mi_solver_set_params(self._s, C.byref(p)))
         self._params = p
+        self._check(self._lib.hymls_mi_solver_set_basis_storage(self._s, bits))
 
     def SetTolerance(self, tol):
         self._check(self._lib.hymls_mi_solver_set_tolerance(self._s, float(tol)))
@@ -105,6 +124,14 @@ class NativeSolver:
 
     def achievedTol(self):
         return self._lib.hymls_mi_solver_achieved_tol(self._s)
+
+    def getNumRestarts(self):
+        """Arnoldi cycles of the last column after its first one (with "MI Basis Storage" = "single" the cycles that
+        were ended early count too)"""
+        return self._lib.hymls_mi_solver_num_restarts(self._s)
+
+    def getBasisStorage(self):
+        return {v: k for k, v in BASIS_STORAGE.items()}[self._lib.hymls_mi_solver_basis_storage(self._s)]
 
     def ApplyInverse(self, B, X=None):
         """solve K X = B.  B: torch tensor on the device (n,) or (nvec, n) (float64, contiguous), or a numpy array (n,)
@@ -166,6 +193,21 @@ def orthogonalize(P, n, k, V, ldv, w):
     nrm = C.c_double()
     ierr = lib.hymls_mi_orthogonalize(P._h, n, k, V.data_ptr(), ldv, w.data_ptr(), h.ctypes.data_as(C.POINTER(C.c_double)),
                                       C.byref(nrm))
+    if ierr:
+        raise HymlsError(ierr, lib.hymls_mi_last_error(P._h).decode())
+    return h, nrm.value
+
+
+def orthogonalize_f32(P, n, k, V, ldv, w, vnext=None):
+    """the same step against a float basis (hymls_mi_orthogonalize_f32): V a float32 tensor, w a float64 tensor that is
+    orthogonalised in place in FP64, vnext (optional float32 tensor of n entries) receives float32(w / ||w||).
+    Returns (h1 + h2, ||w||)."""
+    lib = bind_solver(P._lib)
+    h = np.zeros(k)
+    nrm = C.c_double()
+    ierr = lib.hymls_mi_orthogonalize_f32(P._h, n, k, V.data_ptr(), ldv, w.data_ptr(),
+                                          vnext.data_ptr() if vnext is not None else None,
+                                          h.ctypes.data_as(C.POINTER(C.c_double)), C.byref(nrm))
     if ierr:
         raise HymlsError(ierr, lib.hymls_mi_last_error(P._h).decode())
     return h, nrm.value

@@ -53,6 +53,21 @@ int hymls_mi_solver_set_tolerance(hymls_mi_solver_t* s, double tol);
 int hymls_mi_solver_solve(hymls_mi_solver_t* s, const double* B, int64_t ldb, double* X, int64_t ldx, int nvec, int on_device);
 int hymls_mi_solver_num_iters(const hymls_mi_solver_t* s);
 double hymls_mi_solver_achieved_tol(const hymls_mi_solver_t* s);
+/* Arnoldi cycles of the last column after its first one (GMRES; 0 for CG).  With FP32 basis storage a cycle that was
+ * ended early (below) counts as a restart like one that filled the basis, and "Maximum Restarts" bounds both kinds. */
+int hymls_mi_solver_num_restarts(const hymls_mi_solver_t* s);
+
+/* Storage of the GMRES basis: 64 (default) keeps FP64 columns, 32 stores them as float (compressed-basis GMRES) and
+ * halves the memory and the traffic of the orthogonalisation.  Every other vector, every inner product and the
+ * Hessenberg matrix stay FP64: a new column is w / ||w|| formed in FP64 and rounded once.  Takes effect with the next
+ * solve, which reallocates the basis.  CG ignores it.  Other values return -2; a library built without the FP32 basis
+ * kernels returns -99 for 32.
+ * With 32 bits the recurrence (Givens) estimate of the residual only ends a cycle: at the tolerance, or as soon as it
+ * has fallen to 1e-5 of the residual the cycle started from (a float basis cannot carry a cycle much further).  The
+ * solve ends only on the explicitly computed residual b - K x at the top of the next cycle, and achieved_tol and the
+ * return status come from that residual, also when the iterations or the restarts run out. */
+int hymls_mi_solver_set_basis_storage(hymls_mi_solver_t* s, int bits);
+int hymls_mi_solver_basis_storage(const hymls_mi_solver_t* s);
 
 /* phase timing with events on the stream (adds a synchronisation at the end of every solve while on).
  * which: 0 whole solve, 1 ApplyInverse, 2 K x, 3 orthogonalisation + updates; seconds summed since profiling was
@@ -67,6 +82,13 @@ double hymls_mi_solver_seconds(const hymls_mi_solver_t* s, int which);
  * ranks (collective). */
 int hymls_mi_orthogonalize(hymls_mi_t* h, int64_t n, int32_t k, const double* V, int64_t ldv, double* w, double* hcoef,
                            double* wnorm);
+
+/* The same step against a basis stored as float (V: device memory, n rows, leading dimension ldv floats).  w is
+ * orthogonalised in place in FP64: every product and sum is FP64 on the widened entries.  vnext (device memory, n
+ * floats) may be null; otherwise it receives (float)(w / ||w||), the column an FP32-basis GMRES stores next.
+ * Returns -99 from a library built without the FP32 basis kernels. */
+int hymls_mi_orthogonalize_f32(hymls_mi_t* h, int64_t n, int32_t k, const float* V, int64_t ldv, double* w, float* vnext,
+                               double* hcoef, double* wnorm);
 
 const char* hymls_mi_solver_last_error(const hymls_mi_solver_t* s);
 void hymls_mi_solver_destroy(hymls_mi_solver_t* s);
