@@ -3757,16 +3757,29 @@ __global__ void __launch_bounds__(64) k_blocks_apply_all(const BlkD* __restrict_
     y[ids[i]] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
   }
 }
+// dynamic LDS of the block-apply kernels (the gathered x of one block): above 64 KiB (orders above 8192 with one vector) a
+// launch needs the kernel's limit raised first, as sblock_kept does
+template <class K>
+static void blocks_apply_lds(K kernel, size_t shm, const char* who) {
+  if (shm > LDS_LIMIT_BYTES)
+    throw Error(-2, std::string(who) + ": a separator block of this order needs " + std::to_string(shm) + " bytes of LDS for its vector, the limit is " +
+                        std::to_string(LDS_LIMIT_BYTES));
+  if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+}
 void blocks_apply_all(int32_t nblk, const BlkD* blocks, int32_t max_nb, const double* x, double* y) {
   if (nblk <= 0) return;
-  hipLaunchKernelGGL(k_blocks_apply_all, dim3(nblk), dim3(64), (size_t)max_nb * sizeof(double), g_stream, blocks, x, y);
+  const size_t shm = (size_t)max_nb * sizeof(double);
+  blocks_apply_lds(k_blocks_apply_all, shm, "blocks_apply_all");
+  hipLaunchKernelGGL(k_blocks_apply_all, dim3(nblk), dim3(64), shm, g_stream, blocks, x, y);
   launch_check();
 }
 
 void blocks_apply(int32_t nb, int32_t nblk, const double* binv, const int32_t* ids, const double* x, double* y) {
   if (nb <= 0 || nblk <= 0) return;
   const int bs = nb <= 64 ? 64 : (nb <= 128 ? 128 : 256);
-  hipLaunchKernelGGL(k_blocks_apply, dim3(nblk), dim3(bs), (size_t)nb * sizeof(double), g_stream, nb, binv, ids, x, y);
+  const size_t shm = (size_t)nb * sizeof(double);
+  blocks_apply_lds(k_blocks_apply, shm, "blocks_apply");
+  hipLaunchKernelGGL(k_blocks_apply, dim3(nblk), dim3(bs), shm, g_stream, nb, binv, ids, x, y);
   launch_check();
 }
 
@@ -3816,6 +3829,8 @@ void blocks_apply_all_mv(int32_t nblk, const BlkD* blocks, int32_t max_nb, const
   int v = 0;
   while (v < nv) {
     int g = nv - v >= 4 ? 4 : (nv - v >= 2 ? 2 : 1);
+    // (a group is halved before it would need more than 64 KiB: the grouped kernels never need their LDS limit raised, and
+    // blocks of an order above 8192 go column by column through blocks_apply_all, which raises its own)
     while (g > 1 && ((size_t)max_nb * g * sizeof(double) > 64 * 1024 || g > mv_group_cap("BLK"))) g >>= 1;
     const double* xv = x + (int64_t)v * ldx;
     double* yv = y + (int64_t)v * ldy;
