@@ -339,6 +339,20 @@ bool merged_solve_fits(const ClassPlan& plan) {
   return true;
 }
 
+// LDS of the fused interior solve for one vector, in doubles: X | C | F (+ R inside) | compact front descriptors (48 B)
+FusedNeed fused_solve_need(const ClassPlan& plan) {
+  const int32_t fronts = (int32_t)(plan.fronts.size() * 6 + 1);
+  return FusedNeed{plan.nI + plan.contrib_size + std::max(plan.max_level_rows, 384) + fronts, fronts};
+}
+
+bool fused_solve_fits(const ClassPlan& plan) {
+  constexpr int32_t LDS_CAP = 12288;  // doubles (96 KiB)
+  bool any_big = false;
+  for (auto& L : plan.big_levels) any_big |= !L.empty();
+  return !(any_big || plan.max_level_rows > dev::FUSED_MAX_ITEMS || fused_solve_need(plan).total > LDS_CAP || plan.nI == 0 ||
+           plan.fw_items.empty());
+}
+
 MergedSolve::~MergedSolve() { dev::free(d_subs); dev::free(d_fw); dev::free(d_bw); }
 
 void MergedSolve::build(const std::vector<std::pair<int32_t, const BatchedLU*>>& classes) {
@@ -1859,28 +1873,23 @@ void LevelSolver::build_schur_setup() {
   fine("(pull lists) uploads + allocations");
   lap("pull lists");
   // ---- tables of the fused interior solve (classes whose vectors fit in LDS)
-  constexpr int32_t LDS_CAP = 12288;  // doubles (96 KiB)
   std::vector<dev::PlanD> plans;
   std::vector<dev::FusedSub> subs;
   cls_fused_.assign(cls_.size(), 0);
   fused_lds_ = 0; fused_front_lds_ = 0; fused_vec_lds_ = 0;
   for (size_t c = 0; c < cls_.size(); c++) {
     Cls& C = *cls_[c];
-    const int32_t need = C.lu.plan.nI + C.lu.plan.contrib_size + std::max(C.lu.plan.max_level_rows, 384) +
-                         (int32_t)(C.lu.plan.fronts.size() * 6 + 1);   // X | C | F (+ R inside) | compact front descriptors (48 B)
-    bool any_big = false;
-    for (auto& L : C.lu.plan.big_levels) any_big |= !L.empty();
-    const bool fused = !(any_big || C.lu.plan.max_level_rows > dev::FUSED_MAX_ITEMS || need > LDS_CAP || C.lu.plan.nI == 0 ||
-                         C.lu.plan.fw_items.empty() || std::getenv("HYMLS_MI_NO_FUSED_SOLVE"));
+    const FusedNeed need = fused_solve_need(C.lu.plan);
+    const bool fused = fused_solve_fits(C.lu.plan) && !std::getenv("HYMLS_MI_NO_FUSED_SOLVE");
     C.lu.packed = fused && !std::getenv("HYMLS_MI_NO_PACKED_PANELS");
     C.lu.contrib_nv = fused ? 1 : dev::NV_MAX;   // (the fused kernel keeps its contribution vectors in LDS)
     C.lu.upload(SCRATCH_BUDGET, true);
     plans.push_back(C.lu.dplan);
     if (!fused) continue;
     cls_fused_[c] = 1;
-    fused_lds_ = std::max(fused_lds_, need);
-    fused_front_lds_ = std::max(fused_front_lds_, (int32_t)(C.lu.plan.fronts.size() * 6 + 1));
-    fused_vec_lds_ = std::max(fused_vec_lds_, need - (int32_t)(C.lu.plan.fronts.size() * 6 + 1));
+    fused_lds_ = std::max(fused_lds_, need.total);
+    fused_front_lds_ = std::max(fused_front_lds_, need.fronts);
+    fused_vec_lds_ = std::max(fused_vec_lds_, need.total - need.fronts);
     for (size_t b = 0; b < C.lu.members.size(); b++)
       subs.push_back(dev::FusedSub{{C.lu.batch.factor + (int64_t)b * C.lu.plan.factor_size}, C.lu.h_xoff[b], (int32_t)c});
   }

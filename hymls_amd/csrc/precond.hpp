@@ -129,6 +129,11 @@ struct MergedSolve {
   int max_nv = 1;   // widest column group the contribution scratch of the batches holds
 };
 bool merged_solve_fits(const ClassPlan& plan);   // every front within the LDS limits of the task kernels
+// LDS of the fused interior solve (dev::interior_solve_fused) for one vector, in doubles: all of it, and the share of the front
+// descriptors, which the _mv kernels do not replicate per vector
+struct FusedNeed { int32_t total, fronts; };
+FusedNeed fused_solve_need(const ClassPlan& plan);
+bool fused_solve_fits(const ClassPlan& plan);    // the class can be solved by the fused kernel (LDS, work items per level, no big fronts)
 
 class Operator {  // something with ApplyInverse on device vectors in its own row ordering
  public:
