@@ -282,7 +282,9 @@ void solve_bwd_tasks(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, c
                      const double* y, double* x);
 
 // ---- several right-hand sides (column-major multivectors, leading dimension ld, nv columns): the factor panels are
-// streamed once for groups of up to 4 columns (the single-vector kernels with the per-row state replicated)
+// streamed once for groups of up to 4 columns (NV columns of per-row state in one kernel; for the merged level solve and
+// the separator blocks the single-vector entry points are the NV = 1 launches of the same template.  A column's bits do not
+// depend on the group it is solved in)
 constexpr int NV_MAX = 4;
 // lds_doubles: LDS need for one vector, front_doubles: the share of it that is not replicated per vector
 void interior_solve_fused_mv(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, int32_t front_doubles,

@@ -8,13 +8,14 @@
 //                                factor panels (column-major or packed, rows on consecutive lanes) are streamed once
 //     k_interior_fused_io        the same with a neighbouring vector pass of ApplyInverse in its load / store (FusedIO):
 //                                gather of b1; A12 x2, x1 -= A11 \ y1 and the scatter of x1
-//     k_lvl_fwd / k_lvl_bwd      subdomains too large for LDS: one launch per tree level for all classes, a task is a
+//     k_interior_fused_mv<NV>    the same for 2 or 4 right-hand sides (the panels are streamed once per group)
+//     k_lvl_fwd / k_lvl_bwd <NV> subdomains too large for LDS: one launch per tree level for all classes, a task is a
 //                                whole small front or a 64-row tile of a large one
 //     k_solve_* / k_panel_*      the coarse direct solver (one class, one member): small fronts per workgroup,
 //                                wide supernodes as tiled panel-times-vector products with a fixed-order finalize
 //     k_spmv                     CSR SpMV, 1-8 lanes per row + sub-wave shuffle reduction
 //     k_ot                       per-group Householder: 8 lanes per group, dot + axpy
-//     k_blocks_apply_all         dense block inverse times vector for every separator block of a level
+//     k_blocks_apply_all<NV>     dense block inverse times vector for every separator block of a level
 //     k_gather/k_scatter/k_axpby vector glue and exchange packing
 //   setup path:
 //     k_factor_level             multifrontal front: assemble, LU of the pivot block, triangular inverses, panel
@@ -1868,136 +1869,224 @@ void solve_bwd_level(const PlanD& P, const BatchD& B, const int32_t* list, int32
   }
 }
 
+// ------------------------------------------------------------------ several right-hand sides: column groups
+// ApplyInverse with nvec > 1 (Epetra_MultiVector; the reference sizes its containers for numvec, src/HYMLS_MatrixBlock.cpp:
+// 335-344): the factor panels, the dominant bytes of a solve, are streamed ONCE for a group of NV columns -- every panel
+// entry loaded is used for NV multiply-adds.  Vectors are column-major with a leading dimension.  The merged level
+// solve and the separator blocks are each written once, as a template over NV that keeps the per-row state
+// (accumulators, LDS vectors) NV times; their single-vector entry points launch NV = 1.  The fused interior solve has a
+// kernel of its own for NV = 2 and 4 (k_interior_fused_mv).  Every column keeps the same accumulators and the same
+// summation tree at every NV, so a column's bits do not depend on its group.
+constexpr size_t LDS_LIMIT_BYTES = 160 * 1024;
+// widest column group of a launcher (development switch: HYMLS_MI_MV_GROUP_<FUSED|LVL|BLK> = 1, 2 or 4)
+static int mv_group_cap(const char* which) {
+  const char* e = std::getenv((std::string("HYMLS_MI_MV_GROUP_") + which).c_str());
+  return e ? std::max(1, std::atoi(e)) : NV_MAX;
+}
+// The walk over the nv columns: the widest group (4, 2, 1) of the remaining columns for which fits(g) holds and which
+// mv_group_cap(which) allows; launch(G, v) launches columns [v, v + G) with G a std::integral_constant.
+template <class Fits, class Launch>
+static void for_column_groups(int nv, const char* which, Fits fits, Launch launch) {
+  const int cap = mv_group_cap(which);
+  for (int v = 0, g; v < nv; v += g) {
+    g = nv - v >= 4 ? 4 : (nv - v >= 2 ? 2 : 1);
+    while (g > 1 && (!fits(g) || g > cap)) g >>= 1;
+    if (g == 4) launch(std::integral_constant<int, 4>(), v);
+    else if (g == 2) launch(std::integral_constant<int, 2>(), v);
+    else launch(std::integral_constant<int, 1>(), v);
+  }
+}
+
 // ------------------------------------------------------------------ merged level solve
 // (see device.hpp) one workgroup per task, 256 threads.  Tile tasks: lane = row (coalesced 512-byte panel
 // loads), the four waves split the columns, fixed-order reduction through LDS (bitwise reproducible).
+// NV columns with leading dimension ld (unused at NV = 1), LS doubles of LDS each; the contribution vectors of column
+// v of the whole block live cstride doubles behind those of column v - 1, c0 is the first column of this launch.
+template <int NV>
 __global__ void __launch_bounds__(256) k_lvl_fwd(const LvlTask* __restrict__ tasks, const LvlSub* __restrict__ subs,
                                                   const PlanD* __restrict__ plans, const double* __restrict__ x,
-                                                  double* __restrict__ y) {
-  extern __shared__ double f[];
+                                                  double* __restrict__ y, int64_t ld, int32_t LS, int32_t c0) {
+  extern __shared__ double f[];     // [NV][LS]
   const LvlTask T = tasks[blockIdx.x];
   const LvlSub S = subs[T.sub];
   const PlanD* P = plans + S.cls;
   const FrontD F = P->fronts[T.front];
   const int tid = threadIdx.x, w = F.w, rows = F.w + F.ri;
-  const int64_t ld = rows;
+  const int64_t ldp = rows;
   const double* xb = x + S.xoff;
   double* yb = y + S.xoff;
-  const gmptr<double> cb = as_global_rw(S.contrib);
+  const int64_t cs = S.cstride;
+  const gmptr<double> cb = as_global_rw(S.contrib) + (int64_t)c0 * cs;   // contribution vectors of the columns c0 .. c0 + NV - 1 of the whole block
   const gptr<int32_t> aptr = as_global(P->asm_ptr) + F.a_off;
   const gptr<int32_t> asrc = as_global(P->asm_src);
   const gptr<double> Lp = as_global(S.fac) + F.lp_off;
   if (T.r0 < 0) {
     for (int j = tid; j < rows; j += 256) {
-      double v = j < w ? xb[F.c0 + j] : 0.0;
-      for (int t = aptr[j]; t < aptr[j + 1]; t++) v += cb[asrc[t]];
-      f[j] = v;
+#pragma unroll
+      for (int v = 0; v < NV; v++) {
+        double val = j < w ? xb[v * ld + F.c0 + j] : 0.0;
+        for (int t = aptr[j]; t < aptr[j + 1]; t++) val += cb[v * cs + asrc[t]];
+        f[v * LS + j] = val;
+      }
     }
     __syncthreads();
     for (int i = tid; i < rows; i += 256) {
       const int kmax = i < w ? i : w;
-      double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+      double s0[NV], s1[NV], s2[NV], s3[NV];
+#pragma unroll
+      for (int v = 0; v < NV; v++) { s0[v] = 0.0; s1[v] = 0.0; s2[v] = 0.0; s3[v] = 0.0; }
       int k = 0;
       for (; k + 3 < kmax; k += 4) {
-        s0 += Lp[i + ld * k] * f[k];
-        s1 += Lp[i + ld * (k + 1)] * f[k + 1];
-        s2 += Lp[i + ld * (k + 2)] * f[k + 2];
-        s3 += Lp[i + ld * (k + 3)] * f[k + 3];
+        const double l0 = Lp[i + ldp * k], l1 = Lp[i + ldp * (k + 1)], l2 = Lp[i + ldp * (k + 2)], l3 = Lp[i + ldp * (k + 3)];
+#pragma unroll
+        for (int v = 0; v < NV; v++) {
+          s0[v] += l0 * f[v * LS + k]; s1[v] += l1 * f[v * LS + k + 1]; s2[v] += l2 * f[v * LS + k + 2]; s3[v] += l3 * f[v * LS + k + 3];
+        }
       }
-      for (; k < kmax; k++) s0 += Lp[i + ld * k] * f[k];
-      const double s = (s0 + s1) + (s2 + s3);
-      if (i < w) yb[F.c0 + i] = f[i] + s;
-      else cb[F.c_off + i - w] = f[i] - s;
+      for (; k < kmax; k++) {
+        const double l0 = Lp[i + ldp * k];
+#pragma unroll
+        for (int v = 0; v < NV; v++) s0[v] += l0 * f[v * LS + k];
+      }
+#pragma unroll
+      for (int v = 0; v < NV; v++) {
+        const double s = (s0[v] + s1[v]) + (s2[v] + s3[v]);
+        if (i < w) yb[v * ld + F.c0 + i] = f[v * LS + i] + s;
+        else cb[v * cs + F.c_off + i - w] = f[v * LS + i] - s;
+      }
     }
     return;
   }
   const int r0 = T.r0, lane = tid & 63, g = tid >> 6, i = r0 + lane;
   const int kneed = min(w, r0 + 63);                 // row i uses columns k < min(i, w)
-  double* own = f + ((kneed + 7) & ~7);
-  double (*red)[64] = (double (*)[64])(own + 64);
+  const int KP = (kneed + 7) & ~7;
+  // per vector: [KP assembled pivots | 64 own rows | 4 x 64 reduction]
   for (int j = tid; j < kneed; j += 256) {
-    double v = xb[F.c0 + j];
-    for (int t = aptr[j]; t < aptr[j + 1]; t++) v += cb[asrc[t]];
-    f[j] = v;
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+      double val = xb[v * ld + F.c0 + j];
+      for (int t = aptr[j]; t < aptr[j + 1]; t++) val += cb[v * cs + asrc[t]];
+      f[v * LS + j] = val;
+    }
   }
   if (tid < 64 && i < rows) {
-    double v = i < w ? xb[F.c0 + i] : 0.0;
-    for (int t = aptr[i]; t < aptr[i + 1]; t++) v += cb[asrc[t]];
-    own[lane] = v;
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+      double val = i < w ? xb[v * ld + F.c0 + i] : 0.0;
+      for (int t = aptr[i]; t < aptr[i + 1]; t++) val += cb[v * cs + asrc[t]];
+      f[v * LS + KP + lane] = val;
+    }
   }
   __syncthreads();
   const int krow = i < rows ? (i < w ? i : w) : 0;
   const gptr<double> Lr = Lp + (i < rows ? i : 0);
   const int chunk = ((kneed + 31) / 32) * 8;
   const int kb = g * chunk, ke = min(kb + chunk, kneed);
-  double acc[8];
+  double acc[8][NV];
 #pragma unroll
-  for (int u = 0; u < 8; u++) acc[u] = 0.0;
+  for (int u = 0; u < 8; u++)
+#pragma unroll
+    for (int v = 0; v < NV; v++) acc[u][v] = 0.0;
   int k = kb;
   for (; k + 7 < ke; k += 8) {
     double l[8];
 #pragma unroll
-    for (int u = 0; u < 8; u++) l[u] = Lr[ld * (k + u)];
+    for (int u = 0; u < 8; u++) l[u] = Lr[ldp * (k + u)];
 #pragma unroll
-    for (int u = 0; u < 8; u++) if (k + u < krow) acc[u] += l[u] * f[k + u];
+    for (int u = 0; u < 8; u++)
+      if (k + u < krow) {
+#pragma unroll
+        for (int v = 0; v < NV; v++) acc[u][v] += l[u] * f[v * LS + k + u];
+      }
   }
-  for (; k < ke; k++) if (k < krow) acc[0] += Lr[ld * k] * f[k];
-  red[g][lane] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+  for (; k < ke; k++) if (k < krow) {
+    const double l = Lr[ldp * k];
+#pragma unroll
+    for (int v = 0; v < NV; v++) acc[0][v] += l * f[v * LS + k];
+  }
+#pragma unroll
+  for (int v = 0; v < NV; v++)
+    f[v * LS + KP + 64 + g * 64 + lane] = ((acc[0][v] + acc[1][v]) + (acc[2][v] + acc[3][v])) + ((acc[4][v] + acc[5][v]) + (acc[6][v] + acc[7][v]));
   __syncthreads();
   if (g == 0 && i < rows) {
-    const double sum = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
-    if (i < w) yb[F.c0 + i] = own[lane] + sum;
-    else cb[F.c_off + i - w] = own[lane] - sum;
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+      const double* red = f + v * LS + KP + 64;
+      const double sum = (red[lane] + red[64 + lane]) + (red[128 + lane] + red[192 + lane]);
+      const double own = f[v * LS + KP + lane];
+      if (i < w) yb[v * ld + F.c0 + i] = own + sum;
+      else cb[v * cs + F.c_off + i - w] = own - sum;
+    }
   }
 }
 
+template <int NV>
 __global__ void __launch_bounds__(256) k_lvl_bwd(const LvlTask* __restrict__ tasks, const LvlSub* __restrict__ subs,
                                                   const PlanD* __restrict__ plans, const double* __restrict__ y,
-                                                  double* __restrict__ x) {
-  extern __shared__ double f[];
+                                                  double* __restrict__ x, int64_t ld, int32_t LS) {
+  extern __shared__ double f[];     // [NV][LS]
   const LvlTask T = tasks[blockIdx.x];
   const LvlSub S = subs[T.sub];
   const PlanD* P = plans + S.cls;
   const FrontD F = P->fronts[T.front];
   const int tid = threadIdx.x, w = F.w, ri = F.ri;
-  const int64_t ld = w + ri;
+  const int64_t ldp = w + ri;
   double* xb = x + S.xoff;
   const double* yb = y + S.xoff;
   const gptr<int32_t> idx = as_global(P->fidx) + F.idx_off + w;
   const gptr<double> Lp = as_global(S.fac) + F.lp_off;
   const gptr<double> Q = as_global(S.fac) + F.q_off;
   if (T.r0 < 0) {
-    for (int k = tid; k < w + ri; k += 256) f[k] = k < w ? yb[F.c0 + k] : xb[idx[k - w]];
+    for (int k = tid; k < w + ri; k += 256) {
+#pragma unroll
+      for (int v = 0; v < NV; v++) f[v * LS + k] = k < w ? yb[v * ld + F.c0 + k] : xb[v * ld + idx[k - w]];
+    }
     __syncthreads();
     for (int i = tid; i < w; i += 256) {
-      double s = 0.0;
-      for (int k = i; k < w; k++) s += Lp[i + ld * k] * f[k];
-      double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+      double s[NV], s0[NV], s1[NV], s2[NV], s3[NV];
+#pragma unroll
+      for (int v = 0; v < NV; v++) { s[v] = 0.0; s0[v] = 0.0; s1[v] = 0.0; s2[v] = 0.0; s3[v] = 0.0; }
+      for (int k = i; k < w; k++) {
+        const double l = Lp[i + ldp * k];
+#pragma unroll
+        for (int v = 0; v < NV; v++) s[v] += l * f[v * LS + k];
+      }
       int k = 0;
       for (; k + 3 < ri; k += 4) {
-        s0 += Q[i + (int64_t)w * k] * f[w + k];
-        s1 += Q[i + (int64_t)w * (k + 1)] * f[w + k + 1];
-        s2 += Q[i + (int64_t)w * (k + 2)] * f[w + k + 2];
-        s3 += Q[i + (int64_t)w * (k + 3)] * f[w + k + 3];
+        const double q0 = Q[i + (int64_t)w * k], q1 = Q[i + (int64_t)w * (k + 1)], q2 = Q[i + (int64_t)w * (k + 2)], q3 = Q[i + (int64_t)w * (k + 3)];
+#pragma unroll
+        for (int v = 0; v < NV; v++) {
+          s0[v] += q0 * f[v * LS + w + k]; s1[v] += q1 * f[v * LS + w + k + 1]; s2[v] += q2 * f[v * LS + w + k + 2]; s3[v] += q3 * f[v * LS + w + k + 3];
+        }
       }
-      for (; k < ri; k++) s0 += Q[i + (int64_t)w * k] * f[w + k];
-      xb[F.c0 + i] = s - ((s0 + s1) + (s2 + s3));
+      for (; k < ri; k++) {
+        const double q0 = Q[i + (int64_t)w * k];
+#pragma unroll
+        for (int v = 0; v < NV; v++) s0[v] += q0 * f[v * LS + w + k];
+      }
+#pragma unroll
+      for (int v = 0; v < NV; v++) xb[v * ld + F.c0 + i] = s[v] - ((s0[v] + s1[v]) + (s2[v] + s3[v]));
     }
     return;
   }
   const int r0 = T.r0, lane = tid & 63, g = tid >> 6, i = r0 + lane;
   const int nU = w - r0, total = nU + ri;            // columns r0..w-1 of the pivot block, then the U-side panel
-  double (*red)[64] = (double (*)[64])(f + ((total + 7) & ~7));
-  for (int k = tid; k < total; k += 256) f[k] = k < nU ? yb[F.c0 + r0 + k] : xb[idx[k - nU]];
+  const int TP = (total + 7) & ~7;
+  for (int k = tid; k < total; k += 256) {
+#pragma unroll
+    for (int v = 0; v < NV; v++) f[v * LS + k] = k < nU ? yb[v * ld + F.c0 + r0 + k] : xb[v * ld + idx[k - nU]];
+  }
   __syncthreads();
   const int iv = i < w ? i : r0;
-  const gptr<double> Lr = Lp + iv + ld * r0;   // column r0 + kk
+  const gptr<double> Lr = Lp + iv + ldp * r0;   // column r0 + kk
   const gptr<double> Qr = Q + iv;
   const int chunk = ((total + 31) / 32) * 8;
   const int kb = g * chunk, ke = min(kb + chunk, total);
-  double acc[8];
+  double acc[8][NV];
 #pragma unroll
-  for (int u = 0; u < 8; u++) acc[u] = 0.0;
+  for (int u = 0; u < 8; u++)
+#pragma unroll
+    for (int v = 0; v < NV; v++) acc[u][v] = 0.0;
   // pivot-block part of this wave's range
   {
     const int e = min(ke, nU);
@@ -2005,11 +2094,19 @@ __global__ void __launch_bounds__(256) k_lvl_bwd(const LvlTask* __restrict__ tas
     for (; k + 7 < e; k += 8) {
       double l[8];
 #pragma unroll
-      for (int u = 0; u < 8; u++) l[u] = Lr[ld * (k + u)];
+      for (int u = 0; u < 8; u++) l[u] = Lr[ldp * (k + u)];
 #pragma unroll
-      for (int u = 0; u < 8; u++) if (k + u >= lane) acc[u] += l[u] * f[k + u];
+      for (int u = 0; u < 8; u++)
+        if (k + u >= lane) {
+#pragma unroll
+          for (int v = 0; v < NV; v++) acc[u][v] += l[u] * f[v * LS + k + u];
+        }
     }
-    for (; k < e; k++) if (k >= lane) acc[0] += Lr[ld * k] * f[k];
+    for (; k < e; k++) if (k >= lane) {
+      const double l = Lr[ldp * k];
+#pragma unroll
+      for (int v = 0; v < NV; v++) acc[0][v] += l * f[v * LS + k];
+    }
   }
   // U-side panel part
   {
@@ -2019,30 +2116,65 @@ __global__ void __launch_bounds__(256) k_lvl_bwd(const LvlTask* __restrict__ tas
 #pragma unroll
       for (int u = 0; u < 8; u++) l[u] = Qr[(int64_t)w * (k - nU + u)];
 #pragma unroll
-      for (int u = 0; u < 8; u++) acc[u] -= l[u] * f[k + u];
+      for (int u = 0; u < 8; u++)
+#pragma unroll
+        for (int v = 0; v < NV; v++) acc[u][v] -= l[u] * f[v * LS + k + u];
     }
-    for (; k < ke; k++) acc[0] -= Qr[(int64_t)w * (k - nU)] * f[k];
+    for (; k < ke; k++) {
+      const double l = Qr[(int64_t)w * (k - nU)];
+#pragma unroll
+      for (int v = 0; v < NV; v++) acc[0][v] -= l * f[v * LS + k];
+    }
   }
-  red[g][lane] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+#pragma unroll
+  for (int v = 0; v < NV; v++)
+    f[v * LS + TP + g * 64 + lane] = ((acc[0][v] + acc[1][v]) + (acc[2][v] + acc[3][v])) + ((acc[4][v] + acc[5][v]) + (acc[6][v] + acc[7][v]));
   __syncthreads();
-  if (g == 0 && i < w) xb[F.c0 + i] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+  if (g == 0 && i < w) {
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+      const double* red = f + v * LS + TP;
+      xb[v * ld + F.c0 + i] = (red[lane] + red[64 + lane]) + (red[128 + lane] + red[192 + lane]);
+    }
+  }
 }
 
+// columns [c0, c0 + NV) of the block; a, b point at column c0 (forward: a = x, b = y; backward: a = y, b = x)
+template <int NV>
+static void launch_lvl(bool fwd, const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t ls,
+                       const double* a, double* b, int64_t ld, int32_t c0) {
+  const size_t shm = (size_t)ls * NV * sizeof(double);
+  if (fwd) {
+    if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_lvl_fwd<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL(k_lvl_fwd<NV>, dim3(ntasks), dim3(256), shm, g_stream, tasks, subs, plans, a, b, ld, ls, c0);
+  } else {                                           // (the backward sweep reads no contributions)
+    if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_lvl_bwd<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL(k_lvl_bwd<NV>, dim3(ntasks), dim3(256), shm, g_stream, tasks, subs, plans, a, b, ld, ls);
+  }
+  launch_check();
+}
 void solve_fwd_tasks(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
                      const double* x, double* y) {
-  if (ntasks <= 0) return;
-  if ((size_t)lds_doubles * sizeof(double) > 64 * 1024)
-    HIP_CHECK(hipFuncSetAttribute((const void*)k_lvl_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_doubles * sizeof(double))));
-  hipLaunchKernelGGL(k_lvl_fwd, dim3(ntasks), dim3(256), (size_t)lds_doubles * sizeof(double), g_stream, tasks, subs, plans, x, y);
-  launch_check();
+  if (ntasks > 0) launch_lvl<1>(true, tasks, ntasks, subs, plans, lds_doubles, x, y, 0, 0);
 }
 void solve_bwd_tasks(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
                      const double* y, double* x) {
+  if (ntasks > 0) launch_lvl<1>(false, tasks, ntasks, subs, plans, lds_doubles, y, x, 0, 0);
+}
+static void lvl_tasks_mv(bool fwd, const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
+                         const double* a, double* b, int64_t ld, int nv) {
   if (ntasks <= 0) return;
-  if ((size_t)lds_doubles * sizeof(double) > 64 * 1024)
-    HIP_CHECK(hipFuncSetAttribute((const void*)k_lvl_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_doubles * sizeof(double))));
-  hipLaunchKernelGGL(k_lvl_bwd, dim3(ntasks), dim3(256), (size_t)lds_doubles * sizeof(double), g_stream, tasks, subs, plans, y, x);
-  launch_check();
+  // (every column of the block keeps its own contribution vectors between the tree levels: slot = column index)
+  for_column_groups(nv, "LVL", [&](int g) { return (size_t)lds_doubles * g * sizeof(double) <= LDS_LIMIT_BYTES; },
+                    [&](auto G, int v) { launch_lvl<decltype(G)::value>(fwd, tasks, ntasks, subs, plans, lds_doubles, a + (int64_t)v * ld, b + (int64_t)v * ld, ld, v); });
+}
+void solve_fwd_tasks_mv(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
+                        const double* x, double* y, int64_t ld, int nv) {
+  lvl_tasks_mv(true, tasks, ntasks, subs, plans, lds_doubles, x, y, ld, nv);
+}
+void solve_bwd_tasks_mv(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
+                        const double* y, double* x, int64_t ld, int nv) {
+  lvl_tasks_mv(false, tasks, ntasks, subs, plans, lds_doubles, y, x, ld, nv);
 }
 
 // ------------------------------------------------------------------ bordered systems
@@ -2527,20 +2659,11 @@ void interior_solve_fused_f32(int32_t nsub, const FusedSub* subs, const PlanD* p
   launch_fused<float>(nsub, subs, plans, lds_doubles, x, iop);
 }
 
-// ------------------------------------------------------------------ multi-vector variants (several right-hand sides)
-// ApplyInverse with nvec > 1 (Epetra_MultiVector; the reference sizes its containers for numvec, src/HYMLS_MatrixBlock.cpp:
-// 335-344): the factor panels, the dominant bytes of a solve, are streamed ONCE for a group of NV columns -- every panel
-// entry loaded is used for NV multiply-adds.  Vectors are column-major with a leading dimension; the kernels are the
-// single-vector ones with the per-row state (accumulators, LDS vectors) replicated NV times.  A launcher picks the
-// widest group (4, 2, 1) whose LDS fits and walks over the columns.  (Measured and not kept: 16 / 8 panel entries requested per
-// thread ahead of their use instead of 4 -- the 4-column kernel got 10 % slower; it is not short of bytes in flight.)
-constexpr size_t LDS_LIMIT_BYTES = 160 * 1024;
-// widest column group of a launcher (development switch: HYMLS_MI_MV_GROUP_<FUSED|LVL|BLK> = 1, 2 or 4)
-static int mv_group_cap(const char* which) {
-  const char* e = std::getenv((std::string("HYMLS_MI_MV_GROUP_") + which).c_str());
-  return e ? std::max(1, std::atoi(e)) : NV_MAX;
-}
-
+// The same solve for NV = 2 or 4 right-hand sides: the kernel above with the per-row state (accumulators, LDS vectors)
+// kept NV times and the accumulation order unchanged, so a column has the same bits at every NV (DESIGN.md section 8 on why
+// it is a kernel of its own).
+// (Measured and not kept: 16 / 8 panel entries requested per thread ahead of their use instead of 4 -- the 4-column kernel
+// got 10 % slower; it is not short of bytes in flight.)
 template <int NV, class PT>
 __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __restrict__ subs, const PlanD* __restrict__ plans,
                                                             double* __restrict__ x, int64_t ldx) {
@@ -2799,28 +2922,25 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
     for (int i = tid; i < nI; i += 256) xg[v * ldx + i] = X[v * nI + i];
 }
 
-template <int NV, class PT>
-static void launch_fused_mv(int32_t nsub, const FusedSub* subs, const PlanD* plans, size_t shm, double* x, int64_t ldx) {
-  if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_interior_fused_mv<NV, PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-  hipLaunchKernelGGL((k_interior_fused_mv<NV, PT>), dim3(nsub), dim3(256), shm, g_stream, subs, plans, x, ldx);
-  launch_check();
-}
-// lds_doubles: LDS need of one vector; front_doubles: the part of it that holds the front descriptors (not replicated)
+// nv columns in groups.  lds_doubles: LDS need of one vector; front_doubles: the part of it that holds the front
+// descriptors (not replicated)
 template <class PT>
 static void fused_mv_groups(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, int32_t front_doubles,
                             double* x, int64_t ldx, int nv) {
-  if (nsub <= 0 || nv <= 0) return;
+  if (nsub <= 0) return;
   const size_t per = (size_t)(lds_doubles - front_doubles) * sizeof(double), fixed = (size_t)front_doubles * sizeof(double);
-  int v = 0;
-  while (v < nv) {
-    int g = nv - v >= 4 ? 4 : (nv - v >= 2 ? 2 : 1);
-    while (g > 1 && (per * g + fixed > LDS_LIMIT_BYTES || g > mv_group_cap("FUSED"))) g >>= 1;
+  for_column_groups(nv, "FUSED", [&](int g) { return per * g + fixed <= LDS_LIMIT_BYTES; }, [&](auto G, int v) {
+    constexpr int NV = decltype(G)::value;
     double* xv = x + (int64_t)v * ldx;
-    if (g == 4) (launch_fused_mv<4, PT>)(nsub, subs, plans, per * 4 + fixed, xv, ldx);
-    else if (g == 2) (launch_fused_mv<2, PT>)(nsub, subs, plans, per * 2 + fixed, xv, ldx);
-    else launch_fused<PT>(nsub, subs, plans, lds_doubles, xv, nullptr);
-    v += g;
-  }
+    if constexpr (NV == 1) {
+      launch_fused<PT>(nsub, subs, plans, lds_doubles, xv, nullptr);
+    } else {
+      const size_t shm = per * NV + fixed;
+      if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_interior_fused_mv<NV, PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+      hipLaunchKernelGGL((k_interior_fused_mv<NV, PT>), dim3(nsub), dim3(256), shm, g_stream, subs, plans, xv, ldx);
+      launch_check();
+    }
+  });
 }
 void interior_solve_fused_mv(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, int32_t front_doubles,
                              double* x, int64_t ldx, int nv) {
@@ -2829,283 +2949,6 @@ void interior_solve_fused_mv(int32_t nsub, const FusedSub* subs, const PlanD* pl
 void interior_solve_fused_mv_f32(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, int32_t front_doubles,
                                  double* x, int64_t ldx, int nv) {
   fused_mv_groups<float>(nsub, subs, plans, lds_doubles, front_doubles, x, ldx, nv);
-}
-
-// merged level-synchronous solve, NV columns (k_lvl_fwd / k_lvl_bwd with the LDS vectors and accumulators replicated;
-// the contribution vectors of column v live cstride doubles behind those of column v - 1)
-template <int NV>
-__global__ void __launch_bounds__(256) k_lvl_fwd_mv(const LvlTask* __restrict__ tasks, const LvlSub* __restrict__ subs,
-                                                     const PlanD* __restrict__ plans, const double* __restrict__ x,
-                                                     double* __restrict__ y, int64_t ld, int32_t LS, int32_t c0) {
-  extern __shared__ double f[];     // [NV][LS]
-  const LvlTask T = tasks[blockIdx.x];
-  const LvlSub S = subs[T.sub];
-  const PlanD* P = plans + S.cls;
-  const FrontD F = P->fronts[T.front];
-  const int tid = threadIdx.x, w = F.w, rows = F.w + F.ri;
-  const int64_t ldp = rows;
-  const double* xb = x + S.xoff;
-  double* yb = y + S.xoff;
-  const int64_t cs = S.cstride;
-  const gmptr<double> cb = as_global_rw(S.contrib) + (int64_t)c0 * cs;   // contribution vectors of the columns c0 .. c0 + NV - 1 of the whole block
-  const gptr<int32_t> aptr = as_global(P->asm_ptr) + F.a_off;
-  const gptr<int32_t> asrc = as_global(P->asm_src);
-  const gptr<double> Lp = as_global(S.fac) + F.lp_off;
-  if (T.r0 < 0) {
-    for (int j = tid; j < rows; j += 256) {
-#pragma unroll
-      for (int v = 0; v < NV; v++) {
-        double val = j < w ? xb[v * ld + F.c0 + j] : 0.0;
-        for (int t = aptr[j]; t < aptr[j + 1]; t++) val += cb[v * cs + asrc[t]];
-        f[v * LS + j] = val;
-      }
-    }
-    __syncthreads();
-    for (int i = tid; i < rows; i += 256) {
-      const int kmax = i < w ? i : w;
-      double s0[NV], s1[NV], s2[NV], s3[NV];   // (the accumulation order of the single-vector kernel)
-#pragma unroll
-      for (int v = 0; v < NV; v++) { s0[v] = 0.0; s1[v] = 0.0; s2[v] = 0.0; s3[v] = 0.0; }
-      int k = 0;
-      for (; k + 3 < kmax; k += 4) {
-        const double l0 = Lp[i + ldp * k], l1 = Lp[i + ldp * (k + 1)], l2 = Lp[i + ldp * (k + 2)], l3 = Lp[i + ldp * (k + 3)];
-#pragma unroll
-        for (int v = 0; v < NV; v++) {
-          s0[v] += l0 * f[v * LS + k]; s1[v] += l1 * f[v * LS + k + 1]; s2[v] += l2 * f[v * LS + k + 2]; s3[v] += l3 * f[v * LS + k + 3];
-        }
-      }
-      for (; k < kmax; k++) {
-        const double l0 = Lp[i + ldp * k];
-#pragma unroll
-        for (int v = 0; v < NV; v++) s0[v] += l0 * f[v * LS + k];
-      }
-#pragma unroll
-      for (int v = 0; v < NV; v++) {
-        const double s = (s0[v] + s1[v]) + (s2[v] + s3[v]);
-        if (i < w) yb[v * ld + F.c0 + i] = f[v * LS + i] + s;
-        else cb[v * cs + F.c_off + i - w] = f[v * LS + i] - s;
-      }
-    }
-    return;
-  }
-  const int r0 = T.r0, lane = tid & 63, g = tid >> 6, i = r0 + lane;
-  const int kneed = min(w, r0 + 63);
-  const int KP = (kneed + 7) & ~7;
-  // per vector: [KP assembled pivots | 64 own rows | 4 x 64 reduction]
-  for (int j = tid; j < kneed; j += 256) {
-#pragma unroll
-    for (int v = 0; v < NV; v++) {
-      double val = xb[v * ld + F.c0 + j];
-      for (int t = aptr[j]; t < aptr[j + 1]; t++) val += cb[v * cs + asrc[t]];
-      f[v * LS + j] = val;
-    }
-  }
-  if (tid < 64 && i < rows) {
-#pragma unroll
-    for (int v = 0; v < NV; v++) {
-      double val = i < w ? xb[v * ld + F.c0 + i] : 0.0;
-      for (int t = aptr[i]; t < aptr[i + 1]; t++) val += cb[v * cs + asrc[t]];
-      f[v * LS + KP + lane] = val;
-    }
-  }
-  __syncthreads();
-  const int krow = i < rows ? (i < w ? i : w) : 0;
-  const gptr<double> Lr = Lp + (i < rows ? i : 0);
-  const int chunk = ((kneed + 31) / 32) * 8;
-  const int kb = g * chunk, ke = min(kb + chunk, kneed);
-  double acc[8][NV];
-#pragma unroll
-  for (int u = 0; u < 8; u++)
-#pragma unroll
-    for (int v = 0; v < NV; v++) acc[u][v] = 0.0;
-  int k = kb;
-  for (; k + 7 < ke; k += 8) {
-    double l[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) l[u] = Lr[ldp * (k + u)];
-#pragma unroll
-    for (int u = 0; u < 8; u++)
-      if (k + u < krow) {
-#pragma unroll
-        for (int v = 0; v < NV; v++) acc[u][v] += l[u] * f[v * LS + k + u];
-      }
-  }
-  for (; k < ke; k++) if (k < krow) {
-    const double l = Lr[ldp * k];
-#pragma unroll
-    for (int v = 0; v < NV; v++) acc[0][v] += l * f[v * LS + k];
-  }
-#pragma unroll
-  for (int v = 0; v < NV; v++)
-    f[v * LS + KP + 64 + g * 64 + lane] = ((acc[0][v] + acc[1][v]) + (acc[2][v] + acc[3][v])) + ((acc[4][v] + acc[5][v]) + (acc[6][v] + acc[7][v]));
-  __syncthreads();
-  if (g == 0 && i < rows) {
-#pragma unroll
-    for (int v = 0; v < NV; v++) {
-      const double* red = f + v * LS + KP + 64;
-      const double sum = (red[lane] + red[64 + lane]) + (red[128 + lane] + red[192 + lane]);
-      const double own = f[v * LS + KP + lane];
-      if (i < w) yb[v * ld + F.c0 + i] = own + sum;
-      else cb[v * cs + F.c_off + i - w] = own - sum;
-    }
-  }
-}
-
-template <int NV>
-__global__ void __launch_bounds__(256) k_lvl_bwd_mv(const LvlTask* __restrict__ tasks, const LvlSub* __restrict__ subs,
-                                                     const PlanD* __restrict__ plans, const double* __restrict__ y,
-                                                     double* __restrict__ x, int64_t ld, int32_t LS) {
-  extern __shared__ double f[];
-  const LvlTask T = tasks[blockIdx.x];
-  const LvlSub S = subs[T.sub];
-  const PlanD* P = plans + S.cls;
-  const FrontD F = P->fronts[T.front];
-  const int tid = threadIdx.x, w = F.w, ri = F.ri;
-  const int64_t ldp = w + ri;
-  double* xb = x + S.xoff;
-  const double* yb = y + S.xoff;
-  const gptr<int32_t> idx = as_global(P->fidx) + F.idx_off + w;
-  const gptr<double> Lp = as_global(S.fac) + F.lp_off;
-  const gptr<double> Q = as_global(S.fac) + F.q_off;
-  if (T.r0 < 0) {
-    for (int k = tid; k < w + ri; k += 256) {
-#pragma unroll
-      for (int v = 0; v < NV; v++) f[v * LS + k] = k < w ? yb[v * ld + F.c0 + k] : xb[v * ld + idx[k - w]];
-    }
-    __syncthreads();
-    for (int i = tid; i < w; i += 256) {
-      double s[NV], s0[NV], s1[NV], s2[NV], s3[NV];
-#pragma unroll
-      for (int v = 0; v < NV; v++) { s[v] = 0.0; s0[v] = 0.0; s1[v] = 0.0; s2[v] = 0.0; s3[v] = 0.0; }
-      for (int k = i; k < w; k++) {
-        const double l = Lp[i + ldp * k];
-#pragma unroll
-        for (int v = 0; v < NV; v++) s[v] += l * f[v * LS + k];
-      }
-      int k = 0;
-      for (; k + 3 < ri; k += 4) {
-        const double q0 = Q[i + (int64_t)w * k], q1 = Q[i + (int64_t)w * (k + 1)], q2 = Q[i + (int64_t)w * (k + 2)], q3 = Q[i + (int64_t)w * (k + 3)];
-#pragma unroll
-        for (int v = 0; v < NV; v++) {
-          s0[v] += q0 * f[v * LS + w + k]; s1[v] += q1 * f[v * LS + w + k + 1]; s2[v] += q2 * f[v * LS + w + k + 2]; s3[v] += q3 * f[v * LS + w + k + 3];
-        }
-      }
-      for (; k < ri; k++) {
-        const double q0 = Q[i + (int64_t)w * k];
-#pragma unroll
-        for (int v = 0; v < NV; v++) s0[v] += q0 * f[v * LS + w + k];
-      }
-#pragma unroll
-      for (int v = 0; v < NV; v++) xb[v * ld + F.c0 + i] = s[v] - ((s0[v] + s1[v]) + (s2[v] + s3[v]));
-    }
-    return;
-  }
-  const int r0 = T.r0, lane = tid & 63, g = tid >> 6, i = r0 + lane;
-  const int nU = w - r0, total = nU + ri;
-  const int TP = (total + 7) & ~7;
-  for (int k = tid; k < total; k += 256) {
-#pragma unroll
-    for (int v = 0; v < NV; v++) f[v * LS + k] = k < nU ? yb[v * ld + F.c0 + r0 + k] : xb[v * ld + idx[k - nU]];
-  }
-  __syncthreads();
-  const int iv = i < w ? i : r0;
-  const gptr<double> Lr = Lp + iv + ldp * r0;
-  const gptr<double> Qr = Q + iv;
-  const int chunk = ((total + 31) / 32) * 8;
-  const int kb = g * chunk, ke = min(kb + chunk, total);
-  double acc[8][NV];
-#pragma unroll
-  for (int u = 0; u < 8; u++)
-#pragma unroll
-    for (int v = 0; v < NV; v++) acc[u][v] = 0.0;
-  {
-    const int e = min(ke, nU);
-    int k = kb;
-    for (; k + 7 < e; k += 8) {
-      double l[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) l[u] = Lr[ldp * (k + u)];
-#pragma unroll
-      for (int u = 0; u < 8; u++)
-        if (k + u >= lane) {
-#pragma unroll
-          for (int v = 0; v < NV; v++) acc[u][v] += l[u] * f[v * LS + k + u];
-        }
-    }
-    for (; k < e; k++) if (k >= lane) {
-      const double l = Lr[ldp * k];
-#pragma unroll
-      for (int v = 0; v < NV; v++) acc[0][v] += l * f[v * LS + k];
-    }
-  }
-  {
-    int k = max(kb, nU);
-    for (; k + 7 < ke; k += 8) {
-      double l[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) l[u] = Qr[(int64_t)w * (k - nU + u)];
-#pragma unroll
-      for (int u = 0; u < 8; u++)
-#pragma unroll
-        for (int v = 0; v < NV; v++) acc[u][v] -= l[u] * f[v * LS + k + u];
-    }
-    for (; k < ke; k++) {
-      const double l = Qr[(int64_t)w * (k - nU)];
-#pragma unroll
-      for (int v = 0; v < NV; v++) acc[0][v] -= l * f[v * LS + k];
-    }
-  }
-#pragma unroll
-  for (int v = 0; v < NV; v++)
-    f[v * LS + TP + g * 64 + lane] = ((acc[0][v] + acc[1][v]) + (acc[2][v] + acc[3][v])) + ((acc[4][v] + acc[5][v]) + (acc[6][v] + acc[7][v]));
-  __syncthreads();
-  if (g == 0 && i < w) {
-#pragma unroll
-    for (int v = 0; v < NV; v++) {
-      const double* red = f + v * LS + TP;
-      xb[v * ld + F.c0 + i] = (red[lane] + red[64 + lane]) + (red[128 + lane] + red[192 + lane]);
-    }
-  }
-}
-
-template <int NV>
-static void launch_lvl_mv(bool fwd, const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t ls,
-                          const double* a, double* b, int64_t ld, int32_t c0) {
-  const size_t shm = (size_t)ls * NV * sizeof(double);
-  if (fwd) {
-    if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_lvl_fwd_mv<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(k_lvl_fwd_mv<NV>, dim3(ntasks), dim3(256), shm, g_stream, tasks, subs, plans, a, b, ld, ls, c0);
-  } else {
-    if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_lvl_bwd_mv<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(k_lvl_bwd_mv<NV>, dim3(ntasks), dim3(256), shm, g_stream, tasks, subs, plans, a, b, ld, ls);
-  }
-  launch_check();
-}
-static void lvl_tasks_mv(bool fwd, const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
-                         const double* a, double* b, int64_t ld, int nv) {
-  if (ntasks <= 0 || nv <= 0) return;
-  int v = 0;
-  while (v < nv) {
-    int g = nv - v >= 4 ? 4 : (nv - v >= 2 ? 2 : 1);
-    while (g > 1 && ((size_t)lds_doubles * g * sizeof(double) > LDS_LIMIT_BYTES || g > mv_group_cap("LVL"))) g >>= 1;
-    const double* av = a + (int64_t)v * ld;
-    double* bv = b + (int64_t)v * ld;
-    // (every column of the block keeps its own contribution vectors between the tree levels: slot = column index)
-    if (g == 4) launch_lvl_mv<4>(fwd, tasks, ntasks, subs, plans, lds_doubles, av, bv, ld, v);
-    else if (g == 2) launch_lvl_mv<2>(fwd, tasks, ntasks, subs, plans, lds_doubles, av, bv, ld, v);
-    else if (!fwd) solve_bwd_tasks(tasks, ntasks, subs, plans, lds_doubles, av, bv);    // (the backward sweep reads no contributions)
-    else if (v == 0) solve_fwd_tasks(tasks, ntasks, subs, plans, lds_doubles, av, bv);
-    else launch_lvl_mv<1>(fwd, tasks, ntasks, subs, plans, lds_doubles, av, bv, ld, v);
-    v += g;
-  }
-}
-void solve_fwd_tasks_mv(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
-                        const double* x, double* y, int64_t ld, int nv) {
-  lvl_tasks_mv(true, tasks, ntasks, subs, plans, lds_doubles, x, y, ld, nv);
-}
-void solve_bwd_tasks_mv(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
-                        const double* y, double* x, int64_t ld, int nv) {
-  lvl_tasks_mv(false, tasks, ntasks, subs, plans, lds_doubles, y, x, ld, nv);
 }
 
 // ------------------------------------------------------------------ separator-side kernels
@@ -3731,65 +3574,15 @@ __global__ void __launch_bounds__(256) k_blocks_apply(int32_t nb, const double* 
     y[id[i]] = s0 + s1;
   }
 }
-// one wave per block, lane = row, eight columns in flight
-__global__ void __launch_bounds__(64) k_blocks_apply_all(const BlkD* __restrict__ blocks, const double* __restrict__ x, double* __restrict__ y) {
-  extern __shared__ double xs[];
-  const BlkD D = blocks[blockIdx.x];
-  const int nb = D.nb;
-  const gptr<int32_t> ids = as_global(D.ids);          // (pointers out of the descriptor: global memory, see as_global)
-  for (int j = threadIdx.x; j < nb; j += 64) xs[j] = x[ids[j]];
-  __syncthreads();
-  const int i0 = D.r0 < 0 ? 0 : D.r0, i1 = D.r0 < 0 ? nb : min(nb, D.r0 + 64);
-  for (int i = i0 + threadIdx.x; i < i1; i += 64) {
-    const gptr<double> M = as_global(D.binv) + i;
-    double a[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) a[u] = 0.0;
-    int j = 0;
-    for (; j + 7 < nb; j += 8) {
-      double l[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) l[u] = M[(int64_t)nb * (j + u)];
-#pragma unroll
-      for (int u = 0; u < 8; u++) a[u] += l[u] * xs[j + u];
-    }
-    for (; j < nb; j++) a[0] += M[(int64_t)nb * j] * xs[j];
-    y[ids[i]] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-  }
-}
-// dynamic LDS of the block-apply kernels (the gathered x of one block): above 64 KiB (orders above 8192 with one vector) a
-// launch needs the kernel's limit raised first, as sblock_kept does
-template <class K>
-static void blocks_apply_lds(K kernel, size_t shm, const char* who) {
-  if (shm > LDS_LIMIT_BYTES)
-    throw Error(-2, std::string(who) + ": a separator block of this order needs " + std::to_string(shm) + " bytes of LDS for its vector, the limit is " +
-                        std::to_string(LDS_LIMIT_BYTES));
-  if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-}
-void blocks_apply_all(int32_t nblk, const BlkD* blocks, int32_t max_nb, const double* x, double* y) {
-  if (nblk <= 0) return;
-  const size_t shm = (size_t)max_nb * sizeof(double);
-  blocks_apply_lds(k_blocks_apply_all, shm, "blocks_apply_all");
-  hipLaunchKernelGGL(k_blocks_apply_all, dim3(nblk), dim3(64), shm, g_stream, blocks, x, y);
-  launch_check();
-}
-
-void blocks_apply(int32_t nb, int32_t nblk, const double* binv, const int32_t* ids, const double* x, double* y) {
-  if (nb <= 0 || nblk <= 0) return;
-  const int bs = nb <= 64 ? 64 : (nb <= 128 ? 128 : 256);
-  const size_t shm = (size_t)nb * sizeof(double);
-  blocks_apply_lds(k_blocks_apply, shm, "blocks_apply");
-  hipLaunchKernelGGL(k_blocks_apply, dim3(nblk), dim3(bs), shm, g_stream, nb, binv, ids, x, y);
-  launch_check();
-}
-
+// one wave per block, lane = row, eight columns in flight; NV columns of x / y with leading dimensions ldx / ldy, XS
+// doubles of LDS each
 template <int NV>
-__global__ void __launch_bounds__(64) k_blocks_apply_all_mv(const BlkD* __restrict__ blocks, const double* __restrict__ x, int64_t ldx,
-                                                             double* __restrict__ y, int64_t ldy, int32_t XS) {
+__global__ void __launch_bounds__(64) k_blocks_apply_all(const BlkD* __restrict__ blocks, const double* __restrict__ x, int64_t ldx,
+                                                          double* __restrict__ y, int64_t ldy, int32_t XS) {
   extern __shared__ double xs[];   // [NV][XS]
   const BlkD D = blocks[blockIdx.x];
   const int nb = D.nb;
-  const gptr<int32_t> ids = as_global(D.ids);
+  const gptr<int32_t> ids = as_global(D.ids);          // (pointers out of the descriptor: global memory, see as_global)
   for (int j = threadIdx.x; j < nb; j += 64) {
     const int id = ids[j];
 #pragma unroll
@@ -3824,22 +3617,46 @@ __global__ void __launch_bounds__(64) k_blocks_apply_all_mv(const BlkD* __restri
     for (int v = 0; v < NV; v++) y[v * ldy + id] = ((a[0][v] + a[1][v]) + (a[2][v] + a[3][v])) + ((a[4][v] + a[5][v]) + (a[6][v] + a[7][v]));
   }
 }
+// dynamic LDS of the block-apply kernels (the gathered x of one block): above 64 KiB (orders above 8192 with one vector) a
+// launch needs the kernel's limit raised first, as sblock_kept does
+template <class K>
+static void blocks_apply_lds(K kernel, size_t shm, const char* who) {
+  if (shm > LDS_LIMIT_BYTES)
+    throw Error(-2, std::string(who) + ": a separator block of this order needs " + std::to_string(shm) + " bytes of LDS for its vector, the limit is " +
+                        std::to_string(LDS_LIMIT_BYTES));
+  if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+}
+void blocks_apply_all(int32_t nblk, const BlkD* blocks, int32_t max_nb, const double* x, double* y) {
+  if (nblk <= 0) return;
+  const size_t shm = (size_t)max_nb * sizeof(double);
+  blocks_apply_lds(k_blocks_apply_all<1>, shm, "blocks_apply_all");
+  hipLaunchKernelGGL(k_blocks_apply_all<1>, dim3(nblk), dim3(64), shm, g_stream, blocks, x, 0, y, 0, max_nb);
+  launch_check();
+}
 void blocks_apply_all_mv(int32_t nblk, const BlkD* blocks, int32_t max_nb, const double* x, int64_t ldx, double* y, int64_t ldy, int nv) {
-  if (nblk <= 0 || nv <= 0) return;
-  int v = 0;
-  while (v < nv) {
-    int g = nv - v >= 4 ? 4 : (nv - v >= 2 ? 2 : 1);
-    // (a group is halved before it would need more than 64 KiB: the grouped kernels never need their LDS limit raised, and
-    // blocks of an order above 8192 go column by column through blocks_apply_all, which raises its own)
-    while (g > 1 && ((size_t)max_nb * g * sizeof(double) > 64 * 1024 || g > mv_group_cap("BLK"))) g >>= 1;
+  if (nblk <= 0) return;
+  // (a group is halved before it would need more than 64 KiB: the grouped launches never need their LDS limit raised, and
+  // blocks of an order above 8192 go column by column through blocks_apply_all, which raises its own)
+  for_column_groups(nv, "BLK", [&](int g) { return (size_t)max_nb * g * sizeof(double) <= 64 * 1024; }, [&](auto G, int v) {
+    constexpr int NV = decltype(G)::value;
     const double* xv = x + (int64_t)v * ldx;
     double* yv = y + (int64_t)v * ldy;
-    const size_t shm = (size_t)max_nb * g * sizeof(double);
-    if (g == 4) { hipLaunchKernelGGL(k_blocks_apply_all_mv<4>, dim3(nblk), dim3(64), shm, g_stream, blocks, xv, ldx, yv, ldy, max_nb); launch_check(); }
-    else if (g == 2) { hipLaunchKernelGGL(k_blocks_apply_all_mv<2>, dim3(nblk), dim3(64), shm, g_stream, blocks, xv, ldx, yv, ldy, max_nb); launch_check(); }
-    else blocks_apply_all(nblk, blocks, max_nb, xv, yv);
-    v += g;
-  }
+    if constexpr (NV == 1) {
+      blocks_apply_all(nblk, blocks, max_nb, xv, yv);
+    } else {
+      hipLaunchKernelGGL(k_blocks_apply_all<NV>, dim3(nblk), dim3(64), (size_t)max_nb * NV * sizeof(double), g_stream, blocks, xv, ldx, yv, ldy, max_nb);
+      launch_check();
+    }
+  });
+}
+
+void blocks_apply(int32_t nb, int32_t nblk, const double* binv, const int32_t* ids, const double* x, double* y) {
+  if (nb <= 0 || nblk <= 0) return;
+  const int bs = nb <= 64 ? 64 : (nb <= 128 ? 128 : 256);
+  const size_t shm = (size_t)nb * sizeof(double);
+  blocks_apply_lds(k_blocks_apply, shm, "blocks_apply");
+  hipLaunchKernelGGL(k_blocks_apply, dim3(nblk), dim3(bs), shm, g_stream, nb, binv, ids, x, y);
+  launch_check();
 }
 
 }  // namespace dev
