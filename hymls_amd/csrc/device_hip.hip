@@ -313,6 +313,21 @@ template <class T> __device__ inline gptr<T> as_global(const T* q) { return (gpt
 template <class T> using gmptr = T __attribute__((address_space(1)))*;        // writable
 template <class T> __device__ inline gmptr<T> as_global_rw(T* q) { return (gmptr<T>)q; }
 
+// The leftover entries of a k loop behind its unrolled part, as ONE batch instead of one memory round trip each: the (up
+// to N) loads are issued back to back, each under its predicate, and waited for once; then use(u, entry) runs for the
+// entries present in ascending u.  Loads move, additions do not: use() adds into the accumulator of the scalar loop this
+// replaces, in its order, so the bits stay.  An absent entry is skipped -- no load (it may lie outside the panel), no
+// multiply by zero (0 * inf, signed zeros).
+template <int N, class PRED, class LOAD, class USE>
+__device__ __forceinline__ void tail_batch(PRED pred, LOAD load, USE use) {
+  decltype(load(0)) l[N] = {};
+#pragma unroll
+  for (int u = 0; u < N; u++) if (pred(u)) l[u] = load(u);
+#pragma unroll
+  for (int u = 0; u < N; u++) if (pred(u)) use(u, l[u]);
+}
+struct QEntry { double q; int32_t id; };               // a U-side panel entry and the row of x it multiplies
+
 static inline int nblocks(int64_t n, int bs, int cap = 1 << 20) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + bs - 1) / bs, cap)); }
 
 // ------------------------------------------------------------------ vector kernels
@@ -1943,11 +1958,11 @@ __global__ void __launch_bounds__(256) k_lvl_fwd(const LvlTask* __restrict__ tas
           s0[v] += l0 * f[v * LS + k]; s1[v] += l1 * f[v * LS + k + 1]; s2[v] += l2 * f[v * LS + k + 2]; s3[v] += l3 * f[v * LS + k + 3];
         }
       }
-      for (; k < kmax; k++) {
-        const double l0 = Lp[i + ldp * k];
+      tail_batch<3>([&](int u) { return k + u < kmax; }, [&](int u) { return Lp[i + ldp * (k + u)]; },
+                    [&](int u, double l0) {
 #pragma unroll
-        for (int v = 0; v < NV; v++) s0[v] += l0 * f[v * LS + k];
-      }
+                      for (int v = 0; v < NV; v++) s0[v] += l0 * f[v * LS + k + u];
+                    });
 #pragma unroll
       for (int v = 0; v < NV; v++) {
         const double s = (s0[v] + s1[v]) + (s2[v] + s3[v]);
@@ -1999,11 +2014,11 @@ __global__ void __launch_bounds__(256) k_lvl_fwd(const LvlTask* __restrict__ tas
         for (int v = 0; v < NV; v++) acc[u][v] += l[u] * f[v * LS + k + u];
       }
   }
-  for (; k < ke; k++) if (k < krow) {
-    const double l = Lr[ldp * k];
+  tail_batch<7>([&](int u) { return k + u < ke && k + u < krow; }, [&](int u) { return Lr[ldp * (k + u)]; },
+                [&](int u, double l) {
 #pragma unroll
-    for (int v = 0; v < NV; v++) acc[0][v] += l * f[v * LS + k];
-  }
+                  for (int v = 0; v < NV; v++) acc[0][v] += l * f[v * LS + k + u];
+                });
 #pragma unroll
   for (int v = 0; v < NV; v++)
     f[v * LS + KP + 64 + g * 64 + lane] = ((acc[0][v] + acc[1][v]) + (acc[2][v] + acc[3][v])) + ((acc[4][v] + acc[5][v]) + (acc[6][v] + acc[7][v]));
@@ -2046,12 +2061,20 @@ __global__ void __launch_bounds__(256) k_lvl_bwd(const LvlTask* __restrict__ tas
       double s[NV], s0[NV], s1[NV], s2[NV], s3[NV];
 #pragma unroll
       for (int v = 0; v < NV; v++) { s[v] = 0.0; s0[v] = 0.0; s1[v] = 0.0; s2[v] = 0.0; s3[v] = 0.0; }
-      for (int k = i; k < w; k++) {
-        const double l = Lp[i + ldp * k];
+      int k = i;
+      for (; k + 3 < w; k += 4) {                      // four loads in flight, the additions one after the other into s
+        const double l0 = Lp[i + ldp * k], l1 = Lp[i + ldp * (k + 1)], l2 = Lp[i + ldp * (k + 2)], l3 = Lp[i + ldp * (k + 3)];
 #pragma unroll
-        for (int v = 0; v < NV; v++) s[v] += l * f[v * LS + k];
+        for (int v = 0; v < NV; v++) {
+          s[v] += l0 * f[v * LS + k]; s[v] += l1 * f[v * LS + k + 1]; s[v] += l2 * f[v * LS + k + 2]; s[v] += l3 * f[v * LS + k + 3];
+        }
       }
-      int k = 0;
+      tail_batch<3>([&](int u) { return k + u < w; }, [&](int u) { return Lp[i + ldp * (k + u)]; },
+                    [&](int u, double l) {
+#pragma unroll
+                      for (int v = 0; v < NV; v++) s[v] += l * f[v * LS + k + u];
+                    });
+      k = 0;
       for (; k + 3 < ri; k += 4) {
         const double q0 = Q[i + (int64_t)w * k], q1 = Q[i + (int64_t)w * (k + 1)], q2 = Q[i + (int64_t)w * (k + 2)], q3 = Q[i + (int64_t)w * (k + 3)];
 #pragma unroll
@@ -2059,11 +2082,11 @@ __global__ void __launch_bounds__(256) k_lvl_bwd(const LvlTask* __restrict__ tas
           s0[v] += q0 * f[v * LS + w + k]; s1[v] += q1 * f[v * LS + w + k + 1]; s2[v] += q2 * f[v * LS + w + k + 2]; s3[v] += q3 * f[v * LS + w + k + 3];
         }
       }
-      for (; k < ri; k++) {
-        const double q0 = Q[i + (int64_t)w * k];
+      tail_batch<3>([&](int u) { return k + u < ri; }, [&](int u) { return Q[i + (int64_t)w * (k + u)]; },
+                    [&](int u, double q0) {
 #pragma unroll
-        for (int v = 0; v < NV; v++) s0[v] += q0 * f[v * LS + w + k];
-      }
+                      for (int v = 0; v < NV; v++) s0[v] += q0 * f[v * LS + w + k + u];
+                    });
 #pragma unroll
       for (int v = 0; v < NV; v++) xb[v * ld + F.c0 + i] = s[v] - ((s0[v] + s1[v]) + (s2[v] + s3[v]));
     }
@@ -2102,11 +2125,11 @@ __global__ void __launch_bounds__(256) k_lvl_bwd(const LvlTask* __restrict__ tas
           for (int v = 0; v < NV; v++) acc[u][v] += l[u] * f[v * LS + k + u];
         }
     }
-    for (; k < e; k++) if (k >= lane) {
-      const double l = Lr[ldp * k];
+    tail_batch<7>([&](int u) { return k + u < e && k + u >= lane; }, [&](int u) { return Lr[ldp * (k + u)]; },
+                  [&](int u, double l) {
 #pragma unroll
-      for (int v = 0; v < NV; v++) acc[0][v] += l * f[v * LS + k];
-    }
+                    for (int v = 0; v < NV; v++) acc[0][v] += l * f[v * LS + k + u];
+                  });
   }
   // U-side panel part
   {
@@ -2120,11 +2143,11 @@ __global__ void __launch_bounds__(256) k_lvl_bwd(const LvlTask* __restrict__ tas
 #pragma unroll
         for (int v = 0; v < NV; v++) acc[u][v] -= l[u] * f[v * LS + k + u];
     }
-    for (; k < ke; k++) {
-      const double l = Qr[(int64_t)w * (k - nU)];
+    tail_batch<7>([&](int u) { return k + u < ke; }, [&](int u) { return Qr[(int64_t)w * (k - nU + u)]; },
+                  [&](int u, double l) {
 #pragma unroll
-      for (int v = 0; v < NV; v++) acc[0][v] -= l * f[v * LS + k];
-    }
+                    for (int v = 0; v < NV; v++) acc[0][v] -= l * f[v * LS + k + u];
+                  });
   }
 #pragma unroll
   for (int v = 0; v < NV; v++)
@@ -2361,17 +2384,36 @@ __device__ inline PTR uside(PTR base, int packed, int i, int w, int ri, int& c1,
 // the separate kernel with the lane count spmv() picks (spmv_lanes).
 template <int L>
 __device__ __forceinline__ void fused_spmv_rows(int n, int tid, gptr<int32_t> rp, gptr<int32_t> col, gptr<double> val, gptr<double> x, double* y) {
+  // Four row slots of a thread (base, base + rpb, ...) at a time: their row pointers are requested together, then their
+  // first entries, then the x2 values of those, so that a thread's two or three rows cost one chain of round trips, not one
+  // each.  The additions are those of the loop over single rows.
   const int lane = tid % L, rpb = 256 / L;
-  for (int base = 0; base < n; base += rpb) {     // uniform trip count: every lane of a sub-wave takes part in the shuffles
-    const int row = base + tid / L;
-    double s = 0.0;
-    if (row < n) {
-      const int b = rp[row], e = rp[row + 1];
-      for (int k = b + lane; k < e; k += L) s += val[k] * x[col[k]];
+  for (int base = 0; base < n; base += 4 * rpb) { // uniform trip counts: every lane of a sub-wave takes part in the shuffles
+    int k[4], e[4], c[4];
+    double a[4], xv[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int row = base + j * rpb + tid / L;
+      k[j] = 0; e[j] = 0;
+      if (row < n) { k[j] = rp[row] + lane; e[j] = rp[row + 1]; }
     }
 #pragma unroll
-    for (int off = L / 2; off > 0; off >>= 1) s += __shfl_down(s, off, L);
-    if (row < n && lane == 0) y[row] = s + 0.0;
+    for (int j = 0; j < 4; j++) { a[j] = 0.0; c[j] = 0; if (k[j] < e[j]) { a[j] = val[k[j]]; c[j] = col[k[j]]; } }
+#pragma unroll
+    for (int j = 0; j < 4; j++) { xv[j] = 0.0; if (k[j] < e[j]) xv[j] = x[c[j]]; }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (base + j * rpb >= n) break;
+      const int row = base + j * rpb + tid / L;
+      double s = 0.0;
+      if (k[j] < e[j]) {
+        s += a[j] * xv[j];
+        for (int kk = k[j] + L; kk < e[j]; kk += L) s += val[kk] * x[col[kk]];
+      }
+#pragma unroll
+      for (int off = L / 2; off > 0; off >>= 1) s += __shfl_down(s, off, L);
+      if (row < n && lane == 0) y[row] = s + 0.0;
+    }
   }
 }
 // IN / OUT: where the right-hand side comes from and where the solution goes (FusedIO, device.hpp), fixed at compile time
@@ -2468,7 +2510,9 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
 #pragma unroll
           for (int u = 0; u < 4; u++) a[u] += l[u] * f[k + u];
         }
-        for (; k < kmax; k++) a[0] += ldp(p + (c1 * k - tri * ((k * (k + 3)) >> 1))) * f[k];
+        tail_batch<3>([&](int u) { return k + u < kmax; },
+                      [&](int u) { return ldp(p + (c1 * (k + u) - tri * (((k + u) * (k + u + 3)) >> 1))); },
+                      [&](int u, double l) { a[0] += l * f[k + u]; });
         const double sum = (a[0] + a[1]) + (a[2] + a[3]);
         if (r < w) X[F.c0 + r] = f[r] + sum; else C[F.c_off + r - w] -= sum;
       }
@@ -2490,7 +2534,8 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
           const double l0 = at(k), l1 = at(k + KG), l2 = at(k + 2 * KG), l3 = at(k + 3 * KG);
           a0 += l0 * f[k]; a1 += l1 * f[k + KG]; a2 += l2 * f[k + 2 * KG]; a3 += l3 * f[k + 3 * KG];
         }
-        for (; k < kmax; k += KG) a0 += at(k) * f[k];
+        tail_batch<3>([&](int u) { return k + u * KG < kmax; }, [&](int u) { return at(k + u * KG); },
+                      [&](int u, double l) { a0 += l * f[k + u * KG]; });
       }
       R[kg * RT + it] = (a0 + a1) + (a2 + a3);
       __syncthreads();
@@ -2529,7 +2574,9 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
 #pragma unroll
           for (int u = 0; u < 4; u++) a[u] += l[u] * Xs[k + u];
         }
-        for (; k < w; k++) a[0] += ldp(p + (c1 * k + tri * ((k * (k + 1)) >> 1))) * Xs[k];
+        tail_batch<3>([&](int u) { return k + u < w; },
+                      [&](int u) { return ldp(p + (c1 * (k + u) + tri * (((k + u) * (k + u + 1)) >> 1))); },
+                      [&](int u, double l) { a[0] += l * Xs[k + u]; });
         const gptr<PT> qv = fac + F.q_off + i;
         const gptr<int32_t> idx = fidx + F.idx_off + w;
         k = 0;
@@ -2540,7 +2587,9 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
 #pragma unroll
           for (int u = 0; u < 4; u++) a[u] -= l[u] * X[id[u]];
         }
-        for (; k < ri; k++) a[0] -= ldp(qv + (int64_t)w * k) * X[idx[k]];
+        tail_batch<3>([&](int u) { return k + u < ri; },
+                      [&](int u) { return QEntry{ldp(qv + (int64_t)w * (k + u)), idx[k + u]}; },
+                      [&](int u, QEntry e) { a[0] -= e.q * X[e.id]; });
         Fv[it] = (a[0] + a[1]) + (a[2] + a[3]);     // F is free during the backward sweep
       }
       __syncthreads();   // every read of this level's pivot values is done
@@ -2565,7 +2614,8 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
           const double l0 = at(k), l1 = at(k + KG), l2 = at(k + 2 * KG), l3 = at(k + 3 * KG);
           a0 += l0 * Xs[k]; a1 += l1 * Xs[k + KG]; a2 += l2 * Xs[k + 2 * KG]; a3 += l3 * Xs[k + 3 * KG];
         }
-        for (; k < w; k += KG) a0 += at(k) * Xs[k];
+        tail_batch<3>([&](int u) { return k + u * KG < w; }, [&](int u) { return at(k + u * KG); },
+                      [&](int u, double l) { a0 += l * Xs[k + u * KG]; });
         const gptr<PT> qv = fac + F.q_off + i;
         const gptr<int32_t> idx = fidx + F.idx_off + w;
         k = kg;
@@ -2574,7 +2624,9 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
           const int i0 = idx[k], i1 = idx[k + KG], i2 = idx[k + 2 * KG], i3 = idx[k + 3 * KG];
           a0 -= q0 * X[i0]; a1 -= q1 * X[i1]; a2 -= q2 * X[i2]; a3 -= q3 * X[i3];
         }
-        for (; k < ri; k += KG) a0 -= ldp(qv + (int64_t)w * k) * X[idx[k]];
+        tail_batch<3>([&](int u) { return k + u * KG < ri; },
+                      [&](int u) { return QEntry{ldp(qv + (int64_t)w * (k + u * KG)), idx[k + u * KG]}; },
+                      [&](int u, QEntry e) { a0 -= e.q * X[e.id]; });
       }
       R[kg * RT + it] = (a0 + a1) + (a2 + a3);
       __syncthreads();
@@ -2740,11 +2792,12 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
 #pragma unroll
             for (int v = 0; v < NV; v++) a[u][v] += l[u] * f[v * FS + k + u];
         }
-        for (; k < kmax; k++) {
-          const double l = p[c1 * k - tri * ((k * (k + 3)) >> 1)];
+        tail_batch<3>([&](int u) { return k + u < kmax; },
+                      [&](int u) { return (double)p[c1 * (k + u) - tri * (((k + u) * (k + u + 3)) >> 1)]; },
+                      [&](int u, double l) {
 #pragma unroll
-          for (int v = 0; v < NV; v++) a[0][v] += l * f[v * FS + k];
-        }
+                        for (int v = 0; v < NV; v++) a[0][v] += l * f[v * FS + k + u];
+                      });
 #pragma unroll
         for (int v = 0; v < NV; v++) {
           const double sum = (a[0][v] + a[1][v]) + (a[2][v] + a[3][v]);
@@ -2775,11 +2828,11 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
             a2[v] += l2 * f[v * FS + k + 2 * KG]; a3[v] += l3 * f[v * FS + k + 3 * KG];
           }
         }
-        for (; k < kmax; k += KG) {
-          const double l = at(k);
+        tail_batch<3>([&](int u) { return k + u * KG < kmax; }, [&](int u) { return (double)at(k + u * KG); },
+                      [&](int u, double l) {
 #pragma unroll
-          for (int v = 0; v < NV; v++) a0[v] += l * f[v * FS + k];
-        }
+                        for (int v = 0; v < NV; v++) a0[v] += l * f[v * FS + k + u * KG];
+                      });
       }
 #pragma unroll
       for (int v = 0; v < NV; v++) Fv[v * FS + 128 + kg * RT + it] = (a0[v] + a1[v]) + (a2[v] + a3[v]);
@@ -2824,11 +2877,12 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
 #pragma unroll
             for (int v = 0; v < NV; v++) a[u][v] += l[u] * Xs[v * nI + k + u];
         }
-        for (; k < w; k++) {
-          const double l = p[c1 * k + tri * ((k * (k + 1)) >> 1)];
+        tail_batch<3>([&](int u) { return k + u < w; },
+                      [&](int u) { return (double)p[c1 * (k + u) + tri * (((k + u) * (k + u + 1)) >> 1)]; },
+                      [&](int u, double l) {
 #pragma unroll
-          for (int v = 0; v < NV; v++) a[0][v] += l * Xs[v * nI + k];
-        }
+                        for (int v = 0; v < NV; v++) a[0][v] += l * Xs[v * nI + k + u];
+                      });
         const gptr<PT> qv = fac + F.q_off + i;
         const gptr<int32_t> idx = fidx + F.idx_off + w;
         k = 0;
@@ -2841,11 +2895,12 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
 #pragma unroll
             for (int v = 0; v < NV; v++) a[u][v] -= l[u] * X[v * nI + id[u]];
         }
-        for (; k < ri; k++) {
-          const double l = qv[(int64_t)w * k]; const int id = idx[k];
+        tail_batch<3>([&](int u) { return k + u < ri; },
+                      [&](int u) { return QEntry{(double)qv[(int64_t)w * (k + u)], idx[k + u]}; },
+                      [&](int u, QEntry e) {
 #pragma unroll
-          for (int v = 0; v < NV; v++) a[0][v] -= l * X[v * nI + id];
-        }
+                        for (int v = 0; v < NV; v++) a[0][v] -= e.q * X[v * nI + e.id];
+                      });
 #pragma unroll
         for (int v = 0; v < NV; v++) Fv[v * FS + it] = (a[0][v] + a[1][v]) + (a[2][v] + a[3][v]);
       }
@@ -2879,11 +2934,11 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
             a2[v] += l2 * Xs[v * nI + k + 2 * KG]; a3[v] += l3 * Xs[v * nI + k + 3 * KG];
           }
         }
-        for (; k < w; k += KG) {
-          const double l = at(k);
+        tail_batch<3>([&](int u) { return k + u * KG < w; }, [&](int u) { return (double)at(k + u * KG); },
+                      [&](int u, double l) {
 #pragma unroll
-          for (int v = 0; v < NV; v++) a0[v] += l * Xs[v * nI + k];
-        }
+                        for (int v = 0; v < NV; v++) a0[v] += l * Xs[v * nI + k + u * KG];
+                      });
         const gptr<PT> qv = fac + F.q_off + i;
         const gptr<int32_t> idx = fidx + F.idx_off + w;
         k = kg;
@@ -2895,11 +2950,12 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
             a0[v] -= q0 * X[v * nI + i0]; a1[v] -= q1 * X[v * nI + i1]; a2[v] -= q2 * X[v * nI + i2]; a3[v] -= q3 * X[v * nI + i3];
           }
         }
-        for (; k < ri; k += KG) {
-          const double q0 = qv[(int64_t)w * k]; const int i0 = idx[k];
+        tail_batch<3>([&](int u) { return k + u * KG < ri; },
+                      [&](int u) { return QEntry{(double)qv[(int64_t)w * (k + u * KG)], idx[k + u * KG]}; },
+                      [&](int u, QEntry e) {
 #pragma unroll
-          for (int v = 0; v < NV; v++) a0[v] -= q0 * X[v * nI + i0];
-        }
+                        for (int v = 0; v < NV; v++) a0[v] -= e.q * X[v * nI + e.id];
+                      });
       }
 #pragma unroll
       for (int v = 0; v < NV; v++) Fv[v * FS + 128 + kg * RT + it] = (a0[v] + a1[v]) + (a2[v] + a3[v]);
