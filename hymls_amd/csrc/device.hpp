@@ -82,6 +82,7 @@ struct FrontD {
   int32_t parent, idx_off, rel_off, c_off, a_off, lf_off;
   int32_t ent_begin, ent_end, child_begin, child_end;
   int64_t f_off, lp_off, q_off;
+  int32_t pair = 0;         // paired panels (below): PAIR_L the L side, PAIR_Q the U-side panel Q; only in a packed class
 };
 
 // forward work item of the fused solve with its assembly sources inline: one 16-byte load replaces the chain
@@ -215,6 +216,27 @@ void solve_bwd_level(const PlanD& P, const BatchD& B, const int32_t* list, int32
 HYMLS_HD inline int64_t packed_lower(int64_t w, int64_t i, int64_t k) { return k * (2 * w - k - 1) / 2 + (i - k - 1); }   // i > k
 HYMLS_HD inline int64_t packed_l21(int64_t w, int64_t ri, int64_t i, int64_t k) { return w * (w - 1) / 2 + i + ri * k; }      // row i of L21
 HYMLS_HD inline int64_t packed_upper(int64_t w, int64_t ri, int64_t i, int64_t k) { return w * (w - 1) / 2 + ri * w + k * (k + 1) / 2 + i; }  // i <= k
+// ---- paired panels (FrontD::pair).  The wide levels of the fused solve (more than 128 work items: one thread per row, all
+// columns) read two columns of a row with one load.  For that the panels those levels read keep columns 2j, 2j+1
+// interleaved row by row; no region changes its size or its place.
+//   L21 (PAIR_L)      entry (i, k) at 2 (ri j + i) + (k & 1), j = k >> 1; a last odd column plain behind the pairs
+//   strictly lower    pair-column j holds the rows r >= 2j + 2, both entries: (r, k) at 2 j (w - 1 - j) + 2 (r - 2j - 2)
+//   triangle (PAIR_L) + (k & 1); the floor(w / 2) entries (2j + 1, 2j) without a partner form a strip behind the
+//                     pair-columns, at w (w - 1) / 2 - floor(w / 2) + j
+//   Q (PAIR_Q)        w x ri, rows on lanes as in L21: entry (i, k) at 2 (w j + i) + (k & 1), a last odd column plain
+// The upper triangle (its row loops start at k = i) and the fronts of the k-split levels (a thread group takes every
+// KG-th column) stay as they are.  The L side of a front is paired iff its forward level has more than 128 items, its Q
+// iff its backward level has.
+constexpr int32_t PAIR_L = 1, PAIR_Q = 2;
+HYMLS_HD inline int64_t paired_cols(int64_t ld, int64_t ncol, int64_t i, int64_t k) {   // ld x ncol, column pairs interleaved
+  return k < (ncol & ~(int64_t)1) ? 2 * (ld * (k >> 1) + i) + (k & 1) : ld * k + i;
+}
+HYMLS_HD inline int64_t paired_lower(int64_t w, int64_t i, int64_t k) {   // i > k
+  const int64_t j = k >> 1;
+  return i >= 2 * j + 2 ? 2 * j * (w - 1 - j) + 2 * (i - 2 * j - 2) + (k & 1) : w * (w - 1) / 2 - w / 2 + j;
+}
+HYMLS_HD inline int64_t paired_l21(int64_t w, int64_t ri, int64_t i, int64_t k) { return w * (w - 1) / 2 + paired_cols(ri, w, i, k); }
+HYMLS_HD inline int64_t paired_q(int64_t w, int64_t ri, int64_t i, int64_t k) { return paired_cols(w, ri, i, k); }   // from q_off
 // members [b0, b0+nbc) of the batch; uses the frontal scratch of the chunk as temporary
 void repack_fronts(const PlanD& P, const BatchD& B, int32_t b0, int32_t nbc);
 

@@ -327,6 +327,16 @@ __device__ __forceinline__ void tail_batch(PRED pred, LOAD load, USE use) {
   for (int u = 0; u < N; u++) if (pred(u)) use(u, l[u]);
 }
 struct QEntry { double q; int32_t id; };               // a U-side panel entry and the row of x it multiplies
+// Two neighbouring entries of a paired panel (device.hpp) as ONE load: 16 bytes of an FP64 panel, 8 of an FP32 one.  The
+// alignment stated is that of an entry, which is all a panel inside a slab has.
+template <class PT> struct PanelPair { PT a, b; };
+template <class PT> struct PairVec;
+template <> struct PairVec<double> { typedef double T __attribute__((ext_vector_type(2), aligned(8))); };
+template <> struct PairVec<float> { typedef float T __attribute__((ext_vector_type(2), aligned(4))); };
+template <class PT> __device__ __forceinline__ PanelPair<PT> load_pair(gptr<PT> q) {
+  const typename PairVec<PT>::T v = *(gptr<typename PairVec<PT>::T>)q;
+  return PanelPair<PT>{v.x, v.y};
+}
 
 static inline int nblocks(int64_t n, int bs, int cap = 1 << 20) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + bs - 1) / bs, cap)); }
 
@@ -2226,11 +2236,11 @@ double dot(int64_t n, const double* x, const double* y) {
 
 // panel entries of a front in either layout (device.hpp)
 struct PanelRef {
-  const double* lp; const double* q; int64_t w, ri, ld; int packed;
-  __device__ double linv(int i, int k) const { return packed ? lp[packed_lower(w, i, k)] : lp[i + ld * k]; }            // i > k
+  const double* lp; const double* q; int64_t w, ri, ld; int packed, pair;   // pair: FrontD::pair of a packed class, else 0
+  __device__ double linv(int i, int k) const { return packed ? lp[(pair & PAIR_L) ? paired_lower(w, i, k) : packed_lower(w, i, k)] : lp[i + ld * k]; }   // i > k
   __device__ double uinv(int i, int k) const { return packed ? lp[packed_upper(w, ri, i, k)] : lp[i + ld * k]; }        // i <= k
-  __device__ double pl(int j, int k) const { return packed ? lp[packed_l21(w, ri, j, k)] : lp[(w + j) + ld * k]; }       // row j of L21 L11^{-1}
-  __device__ double qu(int i, int j) const { return q[i + w * j]; }                                                     // U11^{-1} U12
+  __device__ double pl(int j, int k) const { return packed ? lp[(pair & PAIR_L) ? paired_l21(w, ri, j, k) : packed_l21(w, ri, j, k)] : lp[(w + j) + ld * k]; }   // row j of L21 L11^{-1}
+  __device__ double qu(int i, int j) const { return (pair & PAIR_Q) ? q[paired_q(w, ri, i, j)] : q[i + w * j]; }         // U11^{-1} U12
 };
 __global__ void __launch_bounds__(256) k_solve_transposed(PlanD P, BatchD B, const int32_t* __restrict__ order, int32_t nfronts,
                                                            double* __restrict__ x) {
@@ -2243,7 +2253,7 @@ __global__ void __launch_bounds__(256) k_solve_transposed(PlanD P, BatchD B, con
   for (int q = 0; q < nfronts; q++) {
     const FrontD F = P.fronts[order[q]];
     const int w = F.w, ri = F.ri;
-    const PanelRef R{fac + F.lp_off, fac + F.q_off, w, ri, w + ri, P.packed};
+    const PanelRef R{fac + F.lp_off, fac + F.q_off, w, ri, w + ri, P.packed, P.packed ? F.pair : 0};
     for (int j = tid; j < w + ri; j += 256) {
       double v = j < w ? xb[F.c0 + j] : 0.0;
       for (int t = P.asm_ptr[F.a_off + j]; t < P.asm_ptr[F.a_off + j + 1]; t++) v += cb[P.asm_src[t]];
@@ -2261,7 +2271,7 @@ __global__ void __launch_bounds__(256) k_solve_transposed(PlanD P, BatchD B, con
   for (int q = nfronts - 1; q >= 0; q--) {
     const FrontD F = P.fronts[order[q]];
     const int w = F.w, ri = F.ri;
-    const PanelRef R{fac + F.lp_off, fac + F.q_off, w, ri, w + ri, P.packed};
+    const PanelRef R{fac + F.lp_off, fac + F.q_off, w, ri, w + ri, P.packed, P.packed ? F.pair : 0};
     const int32_t* idx = P.fidx + F.idx_off;
     for (int k = tid; k < w + ri; k += 256) a[k] = k < w ? xb[F.c0 + k] : xb[idx[k]];
     __syncthreads();
@@ -2284,20 +2294,26 @@ void solve_transposed(const PlanD& P, const BatchD& B, const int32_t* order, int
 
 // ------------------------------------------------------------------ packed panels
 // one workgroup per (front, member): copy the (w+ri) x w panel to the frontal scratch of the member's slot,
-// write it back in the packed order (device.hpp)
+// write it back in the packed order, or the paired one of a front with FrontD::pair (device.hpp); then the U-side panel
+// of a front with PAIR_Q in the same way
 __global__ void __launch_bounds__(256) k_repack(PlanD P, BatchD B, int32_t b0) {
   const FrontD F = P.fronts[blockIdx.x];
   const int slot = blockIdx.y, b = b0 + slot;
   const int64_t w = F.w, ri = F.ri, ld = w + ri, n = ld * w;
   double* Lp = B.factor + (int64_t)b * P.factor_size + F.lp_off;
-  double* tmp = B.scratch + (int64_t)slot * P.scratch_size + F.f_off;   // this front's own frontal matrix: (w+ri+rs)^2 >= (w+ri) w
+  double* tmp = B.scratch + (int64_t)slot * P.scratch_size + F.f_off;   // this front's own frontal matrix: (w+ri+rs)^2 >= (w+ri) w + w ri
+  const bool pl = (F.pair & PAIR_L) != 0, pq = (F.pair & PAIR_Q) != 0;
+  double* Q = B.factor + (int64_t)b * P.factor_size + F.q_off;
   for (int64_t t = threadIdx.x; t < n; t += 256) tmp[t] = Lp[t];
+  if (pq) for (int64_t t = threadIdx.x; t < w * ri; t += 256) tmp[n + t] = Q[t];
   __syncthreads();
   for (int64_t t = threadIdx.x; t < n; t += 256) {
     const int64_t i = t % ld, k = t / ld;
-    const int64_t dst = i >= w ? packed_l21(w, ri, i - w, k) : (i > k ? packed_lower(w, i, k) : packed_upper(w, ri, i, k));
+    const int64_t dst = i >= w ? (pl ? paired_l21(w, ri, i - w, k) : packed_l21(w, ri, i - w, k))
+                               : (i > k ? (pl ? paired_lower(w, i, k) : packed_lower(w, i, k)) : packed_upper(w, ri, i, k));
     Lp[dst] = tmp[t];
   }
+  if (pq) for (int64_t t = threadIdx.x; t < w * ri; t += 256) Q[paired_q(w, ri, t % w, t / w)] = tmp[n + t];
 }
 void repack_fronts(const PlanD& P, const BatchD& B, int32_t b0, int32_t nbc) {
   if (P.nfronts <= 0 || nbc <= 0) return;
@@ -2358,7 +2374,17 @@ void round_panels(int64_t n, double* slab, int32_t* flag) {
 // hence no write conflicts and bitwise reproducible results.  A panel ((w+ri) x w, column-major)
 // is read with consecutive rows on consecutive lanes; with few items the k range is split over
 // 2 or 4 thread groups so that small levels still keep many loads in flight.
-struct FusedFront { int32_t c0, w, ri, c_off, a_off, lf_off, idx_off, pad; int64_t lp_off, q_off; };
+struct FusedFront { int32_t c0, w, ri, c_off, a_off, lf_off, idx_off, pad; int64_t lp_off, q_off; };   // pad: FrontD::pair
+// One row of the L side of a paired front (PAIR_L, device.hpp): its kmax = min(r, w) entries are kmax / 2 pairs, pair j
+// at pp[c1 j - 2 tri j^2] -- pivot rows (tri = 1, pair-columns of the triangle) and update rows (tri = 0, L21) in one
+// form, as in lside -- and, for an odd kmax, one single entry at ps (the strip of the triangle, the last column of L21).
+template <class PTR>
+__device__ inline PTR lside_pair(PTR base, int r, int w, int ri, int& c1, int& tri, PTR& ps) {
+  const int low = (w * (w - 1)) >> 1;
+  if (r < w) { c1 = 2 * (w - 3); tri = 1; ps = base + (low - (w >> 1) + ((r - 1) >> 1)); return base + (2 * r - 4); }
+  c1 = 2 * ri; tri = 0; ps = base + (low + ri * (w - 1) + (r - w));
+  return base + (low + 2 * (r - w));
+}
 // addressing of one row of the L-side / U-side panel of a front (plain or packed, device.hpp):
 // L-side entry (r, k) = p[c1 k - tri k (k + 3) / 2], U11^{-1} entry (i, k) = p[c1 k + tri k (k + 1) / 2]
 template <class PTR>
@@ -2438,7 +2464,8 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
   for (int i = tid; i < P.nfronts; i += 256) {
     const FrontD G = P.fronts[i];
     FusedFront f;
-    f.c0 = G.c0; f.w = G.w; f.ri = G.ri; f.c_off = G.c_off; f.a_off = G.a_off; f.lf_off = G.lf_off; f.idx_off = G.idx_off; f.pad = 0;
+    f.c0 = G.c0; f.w = G.w; f.ri = G.ri; f.c_off = G.c_off; f.a_off = G.a_off; f.lf_off = G.lf_off; f.idx_off = G.idx_off;
+    f.pad = P.packed ? G.pair : 0;
     f.lp_off = G.lp_off; f.q_off = G.q_off;
     LF[i] = f;
   }
@@ -2496,23 +2523,41 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
         // entry (r, k) of the L-side panel sits at p[c1 * k - tri * k (k + 3) / 2]: plain columns (tri = 0), or the
         // packed strictly-lower triangle for a pivot row of a packed panel (tri = 1)
         int c1, tri;
-        const gptr<PT> p = lside(fac + F.lp_off, P.packed, r, w, F.ri, c1, tri);
         const double* f = Fv + F.lf_off;
         const int kmax = r < w ? r : w;
         double a[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) a[u] = 0.0;
         int k = 0;
-        for (; k + 3 < kmax; k += 4) {
-          double l[4];
+        if (F.pad & PAIR_L) {
+          // paired panel: the same four columns per trip as two loads, a[u] still gets column k + u; the leftover of up
+          // to three columns is one pair and one single entry, requested together, into a[0] in column order
+          gptr<PT> ps;
+          const gptr<PT> pp = lside_pair(fac + F.lp_off, r, w, F.ri, c1, tri, ps);
+          auto pair_at = [&](int j) { return load_pair<PT>(pp + (c1 * j - tri * 2 * j * j)); };
+          for (; k + 3 < kmax; k += 4) {
+            const PanelPair<PT> l0 = pair_at(k >> 1), l1 = pair_at((k >> 1) + 1);
+            a[0] += (double)l0.a * f[k]; a[1] += (double)l0.b * f[k + 1]; a[2] += (double)l1.a * f[k + 2]; a[3] += (double)l1.b * f[k + 3];
+          }
+          const bool hp = k + 1 < kmax, hs = (kmax & 1) != 0;
+          PanelPair<PT> tl = {}; PT ts = 0;
+          if (hp) tl = pair_at(k >> 1);
+          if (hs) ts = *ps;
+          if (hp) { a[0] += (double)tl.a * f[k]; a[0] += (double)tl.b * f[k + 1]; }
+          if (hs) a[0] += (double)ts * f[kmax - 1];
+        } else {
+          const gptr<PT> p = lside(fac + F.lp_off, P.packed, r, w, F.ri, c1, tri);
+          for (; k + 3 < kmax; k += 4) {
+            double l[4];
 #pragma unroll
-          for (int u = 0; u < 4; u++) l[u] = ldp(p + (c1 * (k + u) - tri * (((k + u) * (k + u + 3)) >> 1)));
+            for (int u = 0; u < 4; u++) l[u] = ldp(p + (c1 * (k + u) - tri * (((k + u) * (k + u + 3)) >> 1)));
 #pragma unroll
-          for (int u = 0; u < 4; u++) a[u] += l[u] * f[k + u];
+            for (int u = 0; u < 4; u++) a[u] += l[u] * f[k + u];
+          }
+          tail_batch<3>([&](int u) { return k + u < kmax; },
+                        [&](int u) { return ldp(p + (c1 * (k + u) - tri * (((k + u) * (k + u + 3)) >> 1))); },
+                        [&](int u, double l) { a[0] += l * f[k + u]; });
         }
-        tail_batch<3>([&](int u) { return k + u < kmax; },
-                      [&](int u) { return ldp(p + (c1 * (k + u) - tri * (((k + u) * (k + u + 3)) >> 1))); },
-                      [&](int u, double l) { a[0] += l * f[k + u]; });
         const double sum = (a[0] + a[1]) + (a[2] + a[3]);
         if (r < w) X[F.c0 + r] = f[r] + sum; else C[F.c_off + r - w] -= sum;
       }
@@ -2577,19 +2622,37 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
         tail_batch<3>([&](int u) { return k + u < w; },
                       [&](int u) { return ldp(p + (c1 * (k + u) + tri * (((k + u) * (k + u + 1)) >> 1))); },
                       [&](int u, double l) { a[0] += l * Xs[k + u]; });
-        const gptr<PT> qv = fac + F.q_off + i;
         const gptr<int32_t> idx = fidx + F.idx_off + w;
         k = 0;
-        for (; k + 3 < ri; k += 4) {
-          double l[4]; int id[4];
+        if (F.pad & PAIR_Q) {
+          // paired Q (device.hpp): pivot rows on lanes, column pairs over ri; accumulators and leftover order as below
+          const gptr<PT> qp = fac + F.q_off + 2 * i;
+          for (; k + 3 < ri; k += 4) {
+            const PanelPair<PT> l0 = load_pair<PT>(qp + w * k), l1 = load_pair<PT>(qp + w * (k + 2));   // pair j = k / 2 at 2 w j
+            int id[4];
 #pragma unroll
-          for (int u = 0; u < 4; u++) { l[u] = ldp(qv + (int64_t)w * (k + u)); id[u] = idx[k + u]; }
+            for (int u = 0; u < 4; u++) id[u] = idx[k + u];
+            a[0] -= (double)l0.a * X[id[0]]; a[1] -= (double)l0.b * X[id[1]]; a[2] -= (double)l1.a * X[id[2]]; a[3] -= (double)l1.b * X[id[3]];
+          }
+          const bool hp = k + 1 < ri, hs = (ri & 1) != 0;
+          PanelPair<PT> tl = {}; PT ts = 0; int i0 = 0, i1 = 0, i2 = 0;
+          if (hp) { tl = load_pair<PT>(qp + w * k); i0 = idx[k]; i1 = idx[k + 1]; }
+          if (hs) { ts = fac[F.q_off + w * (ri - 1) + i]; i2 = idx[ri - 1]; }
+          if (hp) { a[0] -= (double)tl.a * X[i0]; a[0] -= (double)tl.b * X[i1]; }
+          if (hs) a[0] -= (double)ts * X[i2];
+        } else {
+          const gptr<PT> qv = fac + F.q_off + i;
+          for (; k + 3 < ri; k += 4) {
+            double l[4]; int id[4];
 #pragma unroll
-          for (int u = 0; u < 4; u++) a[u] -= l[u] * X[id[u]];
+            for (int u = 0; u < 4; u++) { l[u] = ldp(qv + (int64_t)w * (k + u)); id[u] = idx[k + u]; }
+#pragma unroll
+            for (int u = 0; u < 4; u++) a[u] -= l[u] * X[id[u]];
+          }
+          tail_batch<3>([&](int u) { return k + u < ri; },
+                        [&](int u) { return QEntry{ldp(qv + (int64_t)w * (k + u)), idx[k + u]}; },
+                        [&](int u, QEntry e) { a[0] -= e.q * X[e.id]; });
         }
-        tail_batch<3>([&](int u) { return k + u < ri; },
-                      [&](int u) { return QEntry{ldp(qv + (int64_t)w * (k + u)), idx[k + u]}; },
-                      [&](int u, QEntry e) { a[0] -= e.q * X[e.id]; });
         Fv[it] = (a[0] + a[1]) + (a[2] + a[3]);     // F is free during the backward sweep
       }
       __syncthreads();   // every read of this level's pivot values is done
@@ -2731,7 +2794,8 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
   for (int i = tid; i < P.nfronts; i += 256) {
     const FrontD G = P.fronts[i];
     FusedFront f;
-    f.c0 = G.c0; f.w = G.w; f.ri = G.ri; f.c_off = G.c_off; f.a_off = G.a_off; f.lf_off = G.lf_off; f.idx_off = G.idx_off; f.pad = 0;
+    f.c0 = G.c0; f.w = G.w; f.ri = G.ri; f.c_off = G.c_off; f.a_off = G.a_off; f.lf_off = G.lf_off; f.idx_off = G.idx_off;
+    f.pad = P.packed ? G.pair : 0;
     f.lp_off = G.lp_off; f.q_off = G.q_off;
     LF[i] = f;
   }
@@ -2774,9 +2838,17 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
         const FusedFront& F = LF[item >> 16];
         const int r = item & 0xffff, w = F.w;
         int c1, tri;
-        const gptr<PT> p = lside(fac + F.lp_off, P.packed, r, w, F.ri, c1, tri);
+        // entry (r, kk) of a paired panel (device.hpp) with 8-byte loads: inside pair kk / 2, or the single entry behind them
+        const bool pl = (F.pad & PAIR_L) != 0;
+        gptr<PT> ps = fac + F.lp_off;
+        const gptr<PT> p = pl ? lside_pair(fac + F.lp_off, r, w, F.ri, c1, tri, ps) : lside(fac + F.lp_off, P.packed, r, w, F.ri, c1, tri);
         const double* f = Fv + F.lf_off;
         const int kmax = r < w ? r : w;
+        auto at = [&](int kk) -> PT {
+          if (!pl) return p[c1 * kk - tri * ((kk * (kk + 3)) >> 1)];
+          const int j = kk >> 1;
+          return kk < (kmax & ~1) ? p[c1 * j - tri * 2 * j * j + (kk & 1)] : *ps;
+        };
         double a[4][NV];    // (the accumulation order of the single-vector kernel: bitwise the same column)
 #pragma unroll
         for (int u = 0; u < 4; u++)
@@ -2786,14 +2858,14 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
         for (; k + 3 < kmax; k += 4) {
           double l[4];
 #pragma unroll
-          for (int u = 0; u < 4; u++) l[u] = p[c1 * (k + u) - tri * (((k + u) * (k + u + 3)) >> 1)];
+          for (int u = 0; u < 4; u++) l[u] = at(k + u);
 #pragma unroll
           for (int u = 0; u < 4; u++)
 #pragma unroll
             for (int v = 0; v < NV; v++) a[u][v] += l[u] * f[v * FS + k + u];
         }
         tail_batch<3>([&](int u) { return k + u < kmax; },
-                      [&](int u) { return (double)p[c1 * (k + u) - tri * (((k + u) * (k + u + 3)) >> 1)]; },
+                      [&](int u) { return (double)at(k + u); },
                       [&](int u, double l) {
 #pragma unroll
                         for (int v = 0; v < NV; v++) a[0][v] += l * f[v * FS + k + u];
@@ -2885,18 +2957,20 @@ __global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __res
                       });
         const gptr<PT> qv = fac + F.q_off + i;
         const gptr<int32_t> idx = fidx + F.idx_off + w;
+        const bool pq = (F.pad & PAIR_Q) != 0;   // entry (i, kk) of a paired Q (device.hpp)
+        auto qat = [&](int kk) -> PT { return pq && kk < (ri & ~1) ? qv[2 * w * (kk >> 1) + i + (kk & 1)] : qv[(int64_t)w * kk]; };
         k = 0;
         for (; k + 3 < ri; k += 4) {
           double l[4]; int id[4];
 #pragma unroll
-          for (int u = 0; u < 4; u++) { l[u] = qv[(int64_t)w * (k + u)]; id[u] = idx[k + u]; }
+          for (int u = 0; u < 4; u++) { l[u] = qat(k + u); id[u] = idx[k + u]; }
 #pragma unroll
           for (int u = 0; u < 4; u++)
 #pragma unroll
             for (int v = 0; v < NV; v++) a[u][v] -= l[u] * X[v * nI + id[u]];
         }
         tail_batch<3>([&](int u) { return k + u < ri; },
-                      [&](int u) { return QEntry{(double)qv[(int64_t)w * (k + u)], idx[k + u]}; },
+                      [&](int u) { return QEntry{(double)qat(k + u), idx[k + u]}; },
                       [&](int u, QEntry e) {
 #pragma unroll
                         for (int v = 0; v < NV; v++) a[0][v] -= e.q * X[v * nI + e.id];

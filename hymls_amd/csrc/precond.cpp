@@ -160,6 +160,19 @@ void BatchedLU::upload(int64_t budget, bool with_sblock) {
     fd[s] = dev::FrontD{F.c0, F.w, F.ri, F.rs, F.parent, F.idx_off, F.rel_off, F.c_off, F.a_off, F.lf_off,
                         F.ent_begin, F.ent_end, F.child_begin, F.child_end, F.f_off, F.lp_off, F.q_off};
   }
+#ifdef HYMLS_MI_PAIRED_PANELS
+  // paired panels (device.hpp): per front and side, where the wide branch of the fused solve (more than 128 items in the
+  // level) reads it.  HYMLS_MI_FORCE_PAIRED_PANELS: development switch, pairs every packed class (the kernel lab, whose
+  // harness knows nothing of the layout)
+  if (packed && (paired || std::getenv("HYMLS_MI_FORCE_PAIRED_PANELS"))) {
+    for (size_t s = 0; s < fd.size(); s++) {
+      const int32_t lev = plan.fronts[s].level;
+      if (lev < 0 || lev + 1 >= (int32_t)plan.fw_ptr.size() || lev + 1 >= (int32_t)plan.bw_ptr.size()) continue;
+      if (plan.fw_ptr[lev + 1] - plan.fw_ptr[lev] > 128) fd[s].pair |= dev::PAIR_L;
+      if (plan.bw_ptr[lev + 1] - plan.bw_ptr[lev] > 128) fd[s].pair |= dev::PAIR_Q;
+    }
+  }
+#endif
   auto keep = [&](auto* p) { owned.push_back((void*)p); return p; };
   dplan.nI = plan.nI; dplan.nS = plan.nS; dplan.nfronts = (int32_t)fd.size(); dplan.nent = nent;
   dplan.fronts = keep(dev::upload(fd));
@@ -1882,6 +1895,9 @@ void LevelSolver::build_schur_setup() {
     const FusedNeed need = fused_solve_need(C.lu.plan);
     const bool fused = fused_solve_fits(C.lu.plan) && !std::getenv("HYMLS_MI_NO_FUSED_SOLVE");
     C.lu.packed = fused && !std::getenv("HYMLS_MI_NO_PACKED_PANELS");
+#ifdef HYMLS_MI_PAIRED_PANELS
+    C.lu.paired = C.lu.packed && !std::getenv("HYMLS_MI_NO_PAIRED_PANELS");
+#endif
     C.lu.contrib_nv = fused ? 1 : dev::NV_MAX;   // (the fused kernel keeps its contribution vectors in LDS)
     C.lu.upload(SCRATCH_BUDGET, true);
     plans.push_back(C.lu.dplan);

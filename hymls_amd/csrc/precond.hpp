@@ -91,6 +91,7 @@ struct BatchedLU {
   int32_t nent = 0;
   int32_t chunk = 0;              // members factored per pass
   bool packed = false;            // panels repacked after the factorisation (classes solved by the fused kernel)
+  bool paired = false;            // ... with the panels of the wide levels in column pairs (dev::FrontD::pair; needs packed)
   int contrib_nv = 1;             // columns of contribution scratch (several right-hand sides in the task kernels)
   ~BatchedLU();
   void plan_scratch(int64_t scratch_budget_doubles, bool with_sblock);
