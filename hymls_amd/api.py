@@ -89,6 +89,8 @@ def load_library(path=None):
         "hymls_mi_compute": (C.c_int, [H]),
         "hymls_mi_set_factor_storage": (C.c_int, [H, C.c_int]),
         "hymls_mi_factor_storage": (C.c_int, [H]),
+        "hymls_mi_set_merged_factor_storage": (C.c_int, [H, C.c_int]),
+        "hymls_mi_merged_factor_storage": (C.c_int, [H]),
         "hymls_mi_apply_inverse": (C.c_int, [H, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int]),
         "hymls_mi_set_border": (C.c_int, [H, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
         "hymls_mi_apply_inverse_bordered": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
@@ -282,6 +284,9 @@ class Preconditioner:
         storage = params.get("Preconditioner", {}).get("MI Factor Storage", "double")
         if storage != "double":
             self.SetFactorStorage(storage)
+        storage = params.get("Preconditioner", {}).get("MI Merged Factor Storage", "double")
+        if storage != "double":
+            self.SetMergedFactorStorage(storage)
         if comm is not None:
             comm.attach(self)
             px, py, pz = rank_grid
@@ -457,6 +462,18 @@ class Preconditioner:
 
     def FactorStorage(self):
         return {64: "double", 32: "single"}[self._lib.hymls_mi_factor_storage(self._h)]
+
+    def SetMergedFactorStorage(self, storage):
+        """"double" (default) or "single": the same for the panels of the merged level solve, the subdomain classes too
+        large for the fused interior kernel (include/hymls_mi.h: hymls_mi_set_merged_factor_storage).  Independent of
+        SetFactorStorage."""
+        if storage not in _STORAGE:
+            raise HymlsError(-2, "'MI Merged Factor Storage' must be \"double\" or \"single\", not %r" % (storage,))
+        self._check(self._lib.hymls_mi_set_merged_factor_storage(self._h, _STORAGE[storage]))
+        return 0
+
+    def MergedFactorStorage(self):
+        return {64: "double", 32: "single"}[self._lib.hymls_mi_merged_factor_storage(self._h)]
 
     # --- BorderedOperator (reference src/HYMLS_BorderedOperator.hpp)
     def SetBorder(self, V, W=None, C_=None):

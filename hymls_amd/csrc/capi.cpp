@@ -29,6 +29,7 @@ struct hymls_mi {
   std::unique_ptr<LevelSolver> top;
   bool initialized = false, computed = false;
   int factor_bits = 64;      // storage of the panels of the fused interior solve (hymls_mi_set_factor_storage)
+  int merged_bits = 64;      // ... of the merged level solve (hymls_mi_set_merged_factor_storage)
   int n_init = 0, n_comp = 0, n_apply = 0, n_init_top = 0;
   double t_init = 0, t_comp = 0, t_apply = 0;
   std::string err;
@@ -357,6 +358,7 @@ int hymls_mi_compute(hymls_mi_t* h) {
   API_BEGIN
   const double t0 = now();
   h->top->set_factor_bits(h->factor_bits);
+  h->top->set_merged_bits(h->merged_bits);
   h->top->compute();
   dev::sync();
   h->computed = true;
@@ -378,6 +380,20 @@ int hymls_mi_set_factor_storage(hymls_mi_t* h, int bits) {
   API_END(h)
 }
 int hymls_mi_factor_storage(const hymls_mi_t* h) { return h ? h->factor_bits : 0; }
+
+int hymls_mi_set_merged_factor_storage(hymls_mi_t* h, int bits) {
+  if (!h) return -2;
+  API_BEGIN
+  HYMLS_CHECK(bits == 64 || bits == 32, -2, "merged factor storage: 64 or 32 bits per panel entry");
+#ifndef HYMLS_MI_F32_LEVEL_PANELS
+  HYMLS_CHECK(bits == 64, -99, "this build has no FP32 kernels for the merged level solve (a test-only host simulator)");
+#endif
+  HYMLS_CHECK(bits == 64 || !(h->top && h->top->have_border()), -99,
+              "FP32 merged factor storage is not implemented for bordered systems: remove the border first");
+  if (bits != h->merged_bits) { h->merged_bits = bits; h->computed = false; }
+  API_END(h)
+}
+int hymls_mi_merged_factor_storage(const hymls_mi_t* h) { return h ? h->merged_bits : 0; }
 
 int hymls_mi_apply_inverse(hymls_mi_t* h, const double* B, int64_t ldb, double* X, int64_t ldx, int nvec, int on_device) {
   if (!h) return -2;
@@ -414,6 +430,10 @@ int hymls_mi_apply_inverse(hymls_mi_t* h, const double* B, int64_t ldb, double* 
 
 int hymls_mi_set_border(hymls_mi_t* h, int m, const double* V, int64_t ldv, const double* W, int64_t ldw, const double* C) {
   if (!h) return -2;
+  if (h->merged_bits == 32 && m > 0 && V) {
+    h->err = "SetBorder: bordered systems are not implemented with FP32 merged factor storage (hymls_mi_set_merged_factor_storage)";
+    return -99;
+  }
   if (h->factor_bits == 32 && m > 0 && V) {
     h->err = "SetBorder: bordered systems are not implemented with FP32 factor storage (hymls_mi_set_factor_storage)";
     return -99;
@@ -543,6 +563,7 @@ double hymls_mi_apply_bytes(const hymls_mi_t* h, int which) {
     case 8: return std::min(st.bytes_factor, st.bytes_factor_sparse) + st.bytes_spmv + st.bytes_sep +
                    std::min(st.bytes_coarse, st.bytes_coarse_sparse) + st.bytes_vec;
     case 9: return st.bytes_resident;
+    case 10: return st.bytes_merged;
     default: return st.bytes_factor + st.bytes_spmv + st.bytes_sep + st.bytes_coarse + st.bytes_vec;
   }
 }

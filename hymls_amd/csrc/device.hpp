@@ -275,7 +275,7 @@ void interior_solve_fused(int32_t nsub, const FusedSub* subs, const PlanD* plans
 // nearest into the FP32 slab, which has the same layout with 4-byte elements.  *flag |= FLAG_F32_RANGE when an entry is
 // not finite or exceeds FLT_MAX in magnitude.  The _f32 forms of the fused solve read FusedSub::fac32, widen every entry
 // to double on load and are otherwise the FP64 kernels: same products, same sums, same order.  round_panels rounds the
-// FP64 slab through float in place (test-only switch HYMLS_MI_ROUND_PANELS=1: the yardstick of the bitwise tests).
+// FP64 slab through float in place (test-only switch HYMLS_MI_ROUND_PANELS: the yardstick of the bitwise tests).
 // The host simulator under tests/hostsim has none of these; host code refers to them only under HYMLS_MI_F32_PANELS.
 constexpr int32_t FLAG_F32_RANGE = 4;
 void demote_panels(int64_t n, const double* src, float* dst, int32_t* flag);
@@ -288,8 +288,14 @@ void interior_solve_fused_f32(int32_t nsub, const FusedSub* subs, const PlanD* p
 // level.  A task is one workgroup: a whole small front, or a 64-row tile of a large one (all its columns;
 // the assembly of the pivot entries it needs is fused in, which is why the forward sweep reads x and
 // writes y instead of working in place).
-struct LvlSub { const double* fac; double* contrib; int32_t xoff, cls; int64_t cstride; };   // one (class, member); cstride: distance of
-                                                                                             // the contribution vectors of two columns
+struct LvlSub {                                    // one (class, member)
+  union {
+    const double* fac;                               // factor slab of this member
+    const float* fac32;                              // ... of a class with FP32 panel storage (the _f32 launchers; same offsets, in elements)
+  };
+  double* contrib; int32_t xoff, cls;
+  int64_t cstride;                                   // distance of the contribution vectors of two columns
+};
 struct LvlTask { int32_t sub, front, r0, pad; };   // r0 < 0: whole front; else rows [r0, r0 + 64)
 constexpr int LVL_MAX_ROWS = 6144;                 // w + ri limit of a front on this path (LDS vector).  Measured: with wider
                                                    // fronts (one 216 k-unknown system, root front 7 k wide) a 64-row tile task
@@ -317,6 +323,13 @@ void solve_fwd_tasks_mv(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs
                         const double* x, double* y, int64_t ld, int nv);
 void solve_bwd_tasks_mv(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
                         const double* y, double* x, int64_t ld, int nv);
+// FP32 storage of the panels of the merged level solve (option "MI Merged Factor Storage" = "single", DESIGN.md section
+// 16): the tables point into FP32 slabs (LvlSub::fac32, filled by demote_panels), everything else as above.  Host code
+// refers to these two only under HYMLS_MI_F32_LEVEL_PANELS; the simulators under tests/hostsim and tests/f32_sim have none.
+void solve_fwd_tasks_mv_f32(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
+                            const double* x, double* y, int64_t ld, int nv);
+void solve_bwd_tasks_mv_f32(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
+                            const double* y, double* x, int64_t ld, int nv);
 
 // ---- separator-side kernels
 // Householder per owned group on a level separator vector: x <- 2 w (w.x) - x

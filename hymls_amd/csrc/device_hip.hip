@@ -9,7 +9,7 @@
 //     k_interior_fused_io        the same with a neighbouring vector pass of ApplyInverse in its load / store (FusedIO):
 //                                gather of b1; A12 x2, x1 -= A11 \ y1 and the scatter of x1
 //     k_interior_fused_mv<NV>    the same for 2 or 4 right-hand sides (the panels are streamed once per group)
-//     k_lvl_fwd / k_lvl_bwd <NV> subdomains too large for LDS: one launch per tree level for all classes, a task is a
+//     k_lvl_fwd / k_lvl_bwd <NV, PT> subdomains too large for LDS: one launch per tree level for all classes, a task is a
 //                                whole small front or a 64-row tile of a large one
 //     k_solve_* / k_panel_*      the coarse direct solver (one class, one member): small fronts per workgroup,
 //                                wide supernodes as tiled panel-times-vector products with a fixed-order finalize
@@ -1903,6 +1903,7 @@ void solve_bwd_level(const PlanD& P, const BatchD& B, const int32_t* list, int32
 // kernel of its own for NV = 2 and 4 (k_interior_fused_mv).  Every column keeps the same accumulators and the same
 // summation tree at every NV, so a column's bits do not depend on its group.
 constexpr size_t LDS_LIMIT_BYTES = 160 * 1024;
+constexpr bool LVL_F32_COLS16_DEFAULT = false;   // tile loops of k_lvl_*<NV, float>: 8 or 16 columns per step
 // widest column group of a launcher (development switch: HYMLS_MI_MV_GROUP_<FUSED|LVL|BLK> = 1, 2 or 4)
 static int mv_group_cap(const char* which) {
   const char* e = std::getenv((std::string("HYMLS_MI_MV_GROUP_") + which).c_str());
@@ -1927,7 +1928,9 @@ static void for_column_groups(int nv, const char* which, Fits fits, Launch launc
 // loads), the four waves split the columns, fixed-order reduction through LDS (bitwise reproducible).
 // NV columns with leading dimension ld (unused at NV = 1), LS doubles of LDS each; the contribution vectors of column
 // v of the whole block live cstride doubles behind those of column v - 1, c0 is the first column of this launch.
-template <int NV>
+// PT: element type of the panels (double, or float for the FP32 slabs of "MI Merged Factor Storage").  A panel entry is
+// widened when it is loaded; vectors, LDS, accumulators and the order of every sum do not depend on PT.
+template <int NV, class PT, bool W16>
 __global__ void __launch_bounds__(256) k_lvl_fwd(const LvlTask* __restrict__ tasks, const LvlSub* __restrict__ subs,
                                                   const PlanD* __restrict__ plans, const double* __restrict__ x,
                                                   double* __restrict__ y, int64_t ld, int32_t LS, int32_t c0) {
@@ -1944,7 +1947,7 @@ __global__ void __launch_bounds__(256) k_lvl_fwd(const LvlTask* __restrict__ tas
   const gmptr<double> cb = as_global_rw(S.contrib) + (int64_t)c0 * cs;   // contribution vectors of the columns c0 .. c0 + NV - 1 of the whole block
   const gptr<int32_t> aptr = as_global(P->asm_ptr) + F.a_off;
   const gptr<int32_t> asrc = as_global(P->asm_src);
-  const gptr<double> Lp = as_global(S.fac) + F.lp_off;
+  const gptr<PT> Lp = as_global((const PT*)(const void*)S.fac) + F.lp_off;
   if (T.r0 < 0) {
     for (int j = tid; j < rows; j += 256) {
 #pragma unroll
@@ -1962,13 +1965,13 @@ __global__ void __launch_bounds__(256) k_lvl_fwd(const LvlTask* __restrict__ tas
       for (int v = 0; v < NV; v++) { s0[v] = 0.0; s1[v] = 0.0; s2[v] = 0.0; s3[v] = 0.0; }
       int k = 0;
       for (; k + 3 < kmax; k += 4) {
-        const double l0 = Lp[i + ldp * k], l1 = Lp[i + ldp * (k + 1)], l2 = Lp[i + ldp * (k + 2)], l3 = Lp[i + ldp * (k + 3)];
+        const double l0 = (double)Lp[i + ldp * k], l1 = (double)Lp[i + ldp * (k + 1)], l2 = (double)Lp[i + ldp * (k + 2)], l3 = (double)Lp[i + ldp * (k + 3)];
 #pragma unroll
         for (int v = 0; v < NV; v++) {
           s0[v] += l0 * f[v * LS + k]; s1[v] += l1 * f[v * LS + k + 1]; s2[v] += l2 * f[v * LS + k + 2]; s3[v] += l3 * f[v * LS + k + 3];
         }
       }
-      tail_batch<3>([&](int u) { return k + u < kmax; }, [&](int u) { return Lp[i + ldp * (k + u)]; },
+      tail_batch<3>([&](int u) { return k + u < kmax; }, [&](int u) { return (double)Lp[i + ldp * (k + u)]; },
                     [&](int u, double l0) {
 #pragma unroll
                       for (int v = 0; v < NV; v++) s0[v] += l0 * f[v * LS + k + u];
@@ -2004,7 +2007,7 @@ __global__ void __launch_bounds__(256) k_lvl_fwd(const LvlTask* __restrict__ tas
   }
   __syncthreads();
   const int krow = i < rows ? (i < w ? i : w) : 0;
-  const gptr<double> Lr = Lp + (i < rows ? i : 0);
+  const gptr<PT> Lr = Lp + (i < rows ? i : 0);
   const int chunk = ((kneed + 31) / 32) * 8;
   const int kb = g * chunk, ke = min(kb + chunk, kneed);
   double acc[8][NV];
@@ -2013,10 +2016,23 @@ __global__ void __launch_bounds__(256) k_lvl_fwd(const LvlTask* __restrict__ tas
 #pragma unroll
     for (int v = 0; v < NV; v++) acc[u][v] = 0.0;
   int k = kb;
+  if constexpr (W16) {                               // sixteen loads in flight; entry u still goes to accumulator u mod 8, in ascending k
+    for (; k + 15 < ke; k += 16) {
+      PT l[16];
+#pragma unroll
+      for (int u = 0; u < 16; u++) l[u] = Lr[ldp * (k + u)];
+#pragma unroll
+      for (int u = 0; u < 16; u++)
+        if (k + u < krow) {
+#pragma unroll
+          for (int v = 0; v < NV; v++) acc[u & 7][v] += (double)l[u] * f[v * LS + k + u];
+        }
+    }
+  }
   for (; k + 7 < ke; k += 8) {
     double l[8];
 #pragma unroll
-    for (int u = 0; u < 8; u++) l[u] = Lr[ldp * (k + u)];
+    for (int u = 0; u < 8; u++) l[u] = (double)Lr[ldp * (k + u)];
 #pragma unroll
     for (int u = 0; u < 8; u++)
       if (k + u < krow) {
@@ -2024,7 +2040,7 @@ __global__ void __launch_bounds__(256) k_lvl_fwd(const LvlTask* __restrict__ tas
         for (int v = 0; v < NV; v++) acc[u][v] += l[u] * f[v * LS + k + u];
       }
   }
-  tail_batch<7>([&](int u) { return k + u < ke && k + u < krow; }, [&](int u) { return Lr[ldp * (k + u)]; },
+  tail_batch<7>([&](int u) { return k + u < ke && k + u < krow; }, [&](int u) { return (double)Lr[ldp * (k + u)]; },
                 [&](int u, double l) {
 #pragma unroll
                   for (int v = 0; v < NV; v++) acc[0][v] += l * f[v * LS + k + u];
@@ -2045,7 +2061,7 @@ __global__ void __launch_bounds__(256) k_lvl_fwd(const LvlTask* __restrict__ tas
   }
 }
 
-template <int NV>
+template <int NV, class PT, bool W16>
 __global__ void __launch_bounds__(256) k_lvl_bwd(const LvlTask* __restrict__ tasks, const LvlSub* __restrict__ subs,
                                                   const PlanD* __restrict__ plans, const double* __restrict__ y,
                                                   double* __restrict__ x, int64_t ld, int32_t LS) {
@@ -2059,8 +2075,8 @@ __global__ void __launch_bounds__(256) k_lvl_bwd(const LvlTask* __restrict__ tas
   double* xb = x + S.xoff;
   const double* yb = y + S.xoff;
   const gptr<int32_t> idx = as_global(P->fidx) + F.idx_off + w;
-  const gptr<double> Lp = as_global(S.fac) + F.lp_off;
-  const gptr<double> Q = as_global(S.fac) + F.q_off;
+  const gptr<PT> Lp = as_global((const PT*)(const void*)S.fac) + F.lp_off;
+  const gptr<PT> Q = as_global((const PT*)(const void*)S.fac) + F.q_off;
   if (T.r0 < 0) {
     for (int k = tid; k < w + ri; k += 256) {
 #pragma unroll
@@ -2073,26 +2089,26 @@ __global__ void __launch_bounds__(256) k_lvl_bwd(const LvlTask* __restrict__ tas
       for (int v = 0; v < NV; v++) { s[v] = 0.0; s0[v] = 0.0; s1[v] = 0.0; s2[v] = 0.0; s3[v] = 0.0; }
       int k = i;
       for (; k + 3 < w; k += 4) {                      // four loads in flight, the additions one after the other into s
-        const double l0 = Lp[i + ldp * k], l1 = Lp[i + ldp * (k + 1)], l2 = Lp[i + ldp * (k + 2)], l3 = Lp[i + ldp * (k + 3)];
+        const double l0 = (double)Lp[i + ldp * k], l1 = (double)Lp[i + ldp * (k + 1)], l2 = (double)Lp[i + ldp * (k + 2)], l3 = (double)Lp[i + ldp * (k + 3)];
 #pragma unroll
         for (int v = 0; v < NV; v++) {
           s[v] += l0 * f[v * LS + k]; s[v] += l1 * f[v * LS + k + 1]; s[v] += l2 * f[v * LS + k + 2]; s[v] += l3 * f[v * LS + k + 3];
         }
       }
-      tail_batch<3>([&](int u) { return k + u < w; }, [&](int u) { return Lp[i + ldp * (k + u)]; },
+      tail_batch<3>([&](int u) { return k + u < w; }, [&](int u) { return (double)Lp[i + ldp * (k + u)]; },
                     [&](int u, double l) {
 #pragma unroll
                       for (int v = 0; v < NV; v++) s[v] += l * f[v * LS + k + u];
                     });
       k = 0;
       for (; k + 3 < ri; k += 4) {
-        const double q0 = Q[i + (int64_t)w * k], q1 = Q[i + (int64_t)w * (k + 1)], q2 = Q[i + (int64_t)w * (k + 2)], q3 = Q[i + (int64_t)w * (k + 3)];
+        const double q0 = (double)Q[i + (int64_t)w * k], q1 = (double)Q[i + (int64_t)w * (k + 1)], q2 = (double)Q[i + (int64_t)w * (k + 2)], q3 = (double)Q[i + (int64_t)w * (k + 3)];
 #pragma unroll
         for (int v = 0; v < NV; v++) {
           s0[v] += q0 * f[v * LS + w + k]; s1[v] += q1 * f[v * LS + w + k + 1]; s2[v] += q2 * f[v * LS + w + k + 2]; s3[v] += q3 * f[v * LS + w + k + 3];
         }
       }
-      tail_batch<3>([&](int u) { return k + u < ri; }, [&](int u) { return Q[i + (int64_t)w * (k + u)]; },
+      tail_batch<3>([&](int u) { return k + u < ri; }, [&](int u) { return (double)Q[i + (int64_t)w * (k + u)]; },
                     [&](int u, double q0) {
 #pragma unroll
                       for (int v = 0; v < NV; v++) s0[v] += q0 * f[v * LS + w + k + u];
@@ -2111,8 +2127,8 @@ __global__ void __launch_bounds__(256) k_lvl_bwd(const LvlTask* __restrict__ tas
   }
   __syncthreads();
   const int iv = i < w ? i : r0;
-  const gptr<double> Lr = Lp + iv + ldp * r0;   // column r0 + kk
-  const gptr<double> Qr = Q + iv;
+  const gptr<PT> Lr = Lp + iv + ldp * r0;   // column r0 + kk
+  const gptr<PT> Qr = Q + iv;
   const int chunk = ((total + 31) / 32) * 8;
   const int kb = g * chunk, ke = min(kb + chunk, total);
   double acc[8][NV];
@@ -2124,10 +2140,23 @@ __global__ void __launch_bounds__(256) k_lvl_bwd(const LvlTask* __restrict__ tas
   {
     const int e = min(ke, nU);
     int k = kb;
+    if constexpr (W16) {
+      for (; k + 15 < e; k += 16) {
+        PT l[16];
+#pragma unroll
+        for (int u = 0; u < 16; u++) l[u] = Lr[ldp * (k + u)];
+#pragma unroll
+        for (int u = 0; u < 16; u++)
+          if (k + u >= lane) {
+#pragma unroll
+            for (int v = 0; v < NV; v++) acc[u & 7][v] += (double)l[u] * f[v * LS + k + u];
+          }
+      }
+    }
     for (; k + 7 < e; k += 8) {
       double l[8];
 #pragma unroll
-      for (int u = 0; u < 8; u++) l[u] = Lr[ldp * (k + u)];
+      for (int u = 0; u < 8; u++) l[u] = (double)Lr[ldp * (k + u)];
 #pragma unroll
       for (int u = 0; u < 8; u++)
         if (k + u >= lane) {
@@ -2135,7 +2164,7 @@ __global__ void __launch_bounds__(256) k_lvl_bwd(const LvlTask* __restrict__ tas
           for (int v = 0; v < NV; v++) acc[u][v] += l[u] * f[v * LS + k + u];
         }
     }
-    tail_batch<7>([&](int u) { return k + u < e && k + u >= lane; }, [&](int u) { return Lr[ldp * (k + u)]; },
+    tail_batch<7>([&](int u) { return k + u < e && k + u >= lane; }, [&](int u) { return (double)Lr[ldp * (k + u)]; },
                   [&](int u, double l) {
 #pragma unroll
                     for (int v = 0; v < NV; v++) acc[0][v] += l * f[v * LS + k + u];
@@ -2144,16 +2173,27 @@ __global__ void __launch_bounds__(256) k_lvl_bwd(const LvlTask* __restrict__ tas
   // U-side panel part
   {
     int k = max(kb, nU);
+    if constexpr (W16) {
+      for (; k + 15 < ke; k += 16) {
+        PT l[16];
+#pragma unroll
+        for (int u = 0; u < 16; u++) l[u] = Qr[(int64_t)w * (k - nU + u)];
+#pragma unroll
+        for (int u = 0; u < 16; u++)
+#pragma unroll
+          for (int v = 0; v < NV; v++) acc[u & 7][v] -= (double)l[u] * f[v * LS + k + u];
+      }
+    }
     for (; k + 7 < ke; k += 8) {
       double l[8];
 #pragma unroll
-      for (int u = 0; u < 8; u++) l[u] = Qr[(int64_t)w * (k - nU + u)];
+      for (int u = 0; u < 8; u++) l[u] = (double)Qr[(int64_t)w * (k - nU + u)];
 #pragma unroll
       for (int u = 0; u < 8; u++)
 #pragma unroll
         for (int v = 0; v < NV; v++) acc[u][v] -= l[u] * f[v * LS + k + u];
     }
-    tail_batch<7>([&](int u) { return k + u < ke; }, [&](int u) { return Qr[(int64_t)w * (k - nU + u)]; },
+    tail_batch<7>([&](int u) { return k + u < ke; }, [&](int u) { return (double)Qr[(int64_t)w * (k - nU + u)]; },
                   [&](int u, double l) {
 #pragma unroll
                     for (int v = 0; v < NV; v++) acc[0][v] -= l * f[v * LS + k + u];
@@ -2173,41 +2213,65 @@ __global__ void __launch_bounds__(256) k_lvl_bwd(const LvlTask* __restrict__ tas
 }
 
 // columns [c0, c0 + NV) of the block; a, b point at column c0 (forward: a = x, b = y; backward: a = y, b = x)
-template <int NV>
-static void launch_lvl(bool fwd, const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t ls,
-                       const double* a, double* b, int64_t ld, int32_t c0) {
+// PT: element type of the slabs the LvlSub table points into (float: LvlSub::fac32)
+// development switch HYMLS_MI_LVL_F32_COLS = 8 or 16: columns per step of the tile loops of the float instantiations
+static bool lvl_f32_cols16() {
+  static const bool on = [] { const char* e = std::getenv("HYMLS_MI_LVL_F32_COLS"); return e ? std::atoi(e) == 16 : LVL_F32_COLS16_DEFAULT; }();
+  return on;
+}
+template <int NV, class PT, bool W16>
+static void launch_lvl_w(bool fwd, const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t ls,
+                         const double* a, double* b, int64_t ld, int32_t c0) {
   const size_t shm = (size_t)ls * NV * sizeof(double);
   if (fwd) {
-    if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_lvl_fwd<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(k_lvl_fwd<NV>, dim3(ntasks), dim3(256), shm, g_stream, tasks, subs, plans, a, b, ld, ls, c0);
+    if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_lvl_fwd<NV, PT, W16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL((k_lvl_fwd<NV, PT, W16>), dim3(ntasks), dim3(256), shm, g_stream, tasks, subs, plans, a, b, ld, ls, c0);
   } else {                                           // (the backward sweep reads no contributions)
-    if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_lvl_bwd<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(k_lvl_bwd<NV>, dim3(ntasks), dim3(256), shm, g_stream, tasks, subs, plans, a, b, ld, ls);
+    if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_lvl_bwd<NV, PT, W16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL((k_lvl_bwd<NV, PT, W16>), dim3(ntasks), dim3(256), shm, g_stream, tasks, subs, plans, a, b, ld, ls);
   }
   launch_check();
 }
+template <int NV, class PT>
+static void launch_lvl(bool fwd, const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t ls,
+                       const double* a, double* b, int64_t ld, int32_t c0) {
+  if constexpr (std::is_same<PT, float>::value) {
+    if (lvl_f32_cols16()) { launch_lvl_w<NV, PT, true>(fwd, tasks, ntasks, subs, plans, ls, a, b, ld, c0); return; }
+  }
+  launch_lvl_w<NV, PT, false>(fwd, tasks, ntasks, subs, plans, ls, a, b, ld, c0);
+}
 void solve_fwd_tasks(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
                      const double* x, double* y) {
-  if (ntasks > 0) launch_lvl<1>(true, tasks, ntasks, subs, plans, lds_doubles, x, y, 0, 0);
+  if (ntasks > 0) launch_lvl<1, double>(true, tasks, ntasks, subs, plans, lds_doubles, x, y, 0, 0);
 }
 void solve_bwd_tasks(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
                      const double* y, double* x) {
-  if (ntasks > 0) launch_lvl<1>(false, tasks, ntasks, subs, plans, lds_doubles, y, x, 0, 0);
+  if (ntasks > 0) launch_lvl<1, double>(false, tasks, ntasks, subs, plans, lds_doubles, y, x, 0, 0);
 }
+template <class PT>
 static void lvl_tasks_mv(bool fwd, const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
                          const double* a, double* b, int64_t ld, int nv) {
   if (ntasks <= 0) return;
   // (every column of the block keeps its own contribution vectors between the tree levels: slot = column index)
   for_column_groups(nv, "LVL", [&](int g) { return (size_t)lds_doubles * g * sizeof(double) <= LDS_LIMIT_BYTES; },
-                    [&](auto G, int v) { launch_lvl<decltype(G)::value>(fwd, tasks, ntasks, subs, plans, lds_doubles, a + (int64_t)v * ld, b + (int64_t)v * ld, ld, v); });
+                    [&](auto G, int v) { launch_lvl<decltype(G)::value, PT>(fwd, tasks, ntasks, subs, plans, lds_doubles, a + (int64_t)v * ld, b + (int64_t)v * ld, ld, v); });
 }
 void solve_fwd_tasks_mv(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
                         const double* x, double* y, int64_t ld, int nv) {
-  lvl_tasks_mv(true, tasks, ntasks, subs, plans, lds_doubles, x, y, ld, nv);
+  lvl_tasks_mv<double>(true, tasks, ntasks, subs, plans, lds_doubles, x, y, ld, nv);
 }
 void solve_bwd_tasks_mv(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
                         const double* y, double* x, int64_t ld, int nv) {
-  lvl_tasks_mv(false, tasks, ntasks, subs, plans, lds_doubles, y, x, ld, nv);
+  lvl_tasks_mv<double>(false, tasks, ntasks, subs, plans, lds_doubles, y, x, ld, nv);
+}
+// the same on FP32 slabs (LvlSub::fac32): every panel entry is widened on load, sums and their order are those above
+void solve_fwd_tasks_mv_f32(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
+                            const double* x, double* y, int64_t ld, int nv) {
+  lvl_tasks_mv<float>(true, tasks, ntasks, subs, plans, lds_doubles, x, y, ld, nv);
+}
+void solve_bwd_tasks_mv_f32(const LvlTask* tasks, int32_t ntasks, const LvlSub* subs, const PlanD* plans, int32_t lds_doubles,
+                            const double* y, double* x, int64_t ld, int nv) {
+  lvl_tasks_mv<float>(false, tasks, ntasks, subs, plans, lds_doubles, y, x, ld, nv);
 }
 
 // ------------------------------------------------------------------ bordered systems

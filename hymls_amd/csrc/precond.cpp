@@ -372,7 +372,10 @@ void MergedSolve::build(const std::vector<std::pair<int32_t, const BatchedLU*>>&
   dev::free(d_subs); dev::free(d_fw); dev::free(d_bw);
   d_subs = nullptr; d_fw = d_bw = nullptr;
   const int small_rows = std::getenv("HYMLS_MI_LVL_SMALL_ROWS") ? std::atoi(std::getenv("HYMLS_MI_LVL_SMALL_ROWS")) : dev::LVL_SMALL_ROWS;
-  std::vector<dev::LvlSub> lsubs;
+  std::vector<dev::LvlSub>& lsubs = h_subs_;
+  lsubs.clear();
+  classes_ = classes;
+  bits = 64;
   std::vector<const ClassPlan*> sub_plan;
   max_nv = dev::NV_MAX;
   std::vector<std::vector<std::pair<int64_t, dev::LvlTask>>> fw, bw;   // per tree level: (cost, task)
@@ -382,7 +385,7 @@ void MergedSolve::build(const std::vector<std::pair<int32_t, const BatchedLU*>>&
     if (fw.size() < nl) { fw.resize(nl); bw.resize(nl); }
     for (size_t b = 0; b < lu.members.size(); b++) {
       const int32_t sub = (int32_t)lsubs.size();
-      lsubs.push_back(dev::LvlSub{lu.batch.factor + (int64_t)b * lu.plan.factor_size,
+      lsubs.push_back(dev::LvlSub{{lu.batch.factor + (int64_t)b * lu.plan.factor_size},
                                   lu.batch.contrib + (int64_t)b * lu.plan.contrib_size, lu.h_xoff[b], cb.first,
                                   (int64_t)lu.members.size() * lu.plan.contrib_size});
       max_nv = std::min(max_nv, lu.contrib_nv);
@@ -437,6 +440,22 @@ void MergedSolve::build(const std::vector<std::pair<int32_t, const BatchedLU*>>&
   d_fw = dev::upload(tf); d_bw = dev::upload(tb);
 }
 
+#if defined(HYMLS_MI_F32_LEVEL_PANELS) && !defined(HYMLS_MI_F32_PANELS)
+#error "HYMLS_MI_F32_LEVEL_PANELS needs the demotion kernels of HYMLS_MI_F32_PANELS"
+#endif
+void MergedSolve::set_storage(int storage_bits) {
+  size_t sub = 0;
+  for (auto& cb : classes_) {
+    const BatchedLU& lu = *cb.second;
+    for (size_t b = 0; b < lu.members.size(); b++, sub++) {
+      if (storage_bits == 32) h_subs_[sub].fac32 = lu.factor32 + (int64_t)b * lu.plan.factor_size;
+      else h_subs_[sub].fac = lu.batch.factor + (int64_t)b * lu.plan.factor_size;
+    }
+  }
+  if (nsubs) dev::h2d(d_subs, h_subs_.data(), h_subs_.size() * sizeof(dev::LvlSub));
+  bits = storage_bits;
+}
+
 // x <- A^{-1} x for every member of every class of the tables, nv columns with leading dimension ld; y: scratch (same shape)
 void MergedSolve::solve(const dev::PlanD* d_plans, double* x, double* y, int64_t ld, int nv) const {
   const int nl = (int)fw_lds.size();
@@ -444,6 +463,15 @@ void MergedSolve::solve(const dev::PlanD* d_plans, double* x, double* y, int64_t
     const int g = std::min(max_nv, nv - v0);
     double* xv = x + (int64_t)v0 * ld;
     double* yv = y + (int64_t)v0 * ld;
+#ifdef HYMLS_MI_F32_LEVEL_PANELS
+    if (bits == 32) {
+      for (int l = 0; l < nl; l++)
+        dev::solve_fwd_tasks_mv_f32(d_fw + fw_off[l], fw_off[l + 1] - fw_off[l], d_subs, d_plans, fw_lds[l], xv, yv, ld, g);
+      for (int l = nl - 1; l >= 0; l--)
+        dev::solve_bwd_tasks_mv_f32(d_bw + bw_off[l], bw_off[l + 1] - bw_off[l], d_subs, d_plans, bw_lds[l], yv, xv, ld, g);
+      continue;
+    }
+#endif
     for (int l = 0; l < nl; l++)
       dev::solve_fwd_tasks_mv(d_fw + fw_off[l], fw_off[l + 1] - fw_off[l], d_subs, d_plans, fw_lds[l], xv, yv, ld, g);
     for (int l = nl - 1; l >= 0; l--)
@@ -2109,6 +2137,7 @@ void LevelSolver::prepare_factor_storage() {
 #ifdef HYMLS_MI_F32_PANELS
   HYMLS_CHECK(factor_bits_ == 64 || bm_ == 0, -99, "FP32 factor storage is not implemented for bordered systems "
                                                    "(the transposed solve reads the FP64 panels)");
+  prepare_merged_storage();
   if (factor_bits_ == 64 && fsubs_bits_ == 64) return;
   dev::sync();   // (slabs may still be read by an ApplyInverse in flight)
   std::vector<dev::FusedSub> subs;
@@ -2132,15 +2161,38 @@ void LevelSolver::prepare_factor_storage() {
   }
 #else
   HYMLS_CHECK(factor_bits_ == 64, -99, "this build has no FP32 panel kernels");
+  prepare_merged_storage();
+#endif
+}
+
+// The same for the classes of the merged level solve, which keep the unpacked panels: FP32 slab held,
+// every chunk demoted into it, the table of merged_ pointed at it, the FP64 slab given back by finish_factor_storage().
+// Nothing else reads the FP64 slab of such a class between two Computes: BatchedLU::solve() runs for the classes that are
+// neither fused nor merged only, and the transposed solve belongs to bordered systems, which are refused here.
+void LevelSolver::prepare_merged_storage() {
+#ifdef HYMLS_MI_F32_LEVEL_PANELS
+  HYMLS_CHECK(merged_bits_ == 64 || bm_ == 0, -99, "FP32 merged factor storage is not implemented for bordered systems "
+                                                   "(the transposed solve reads the FP64 panels)");
+  if (merged_bits_ == 64 && merged_.bits == 64) return;
+  dev::sync();   // (slabs may still be read by an ApplyInverse in flight)
+  for (size_t c = 0; c < cls_.size(); c++) {
+    if (!cls_merged_[c]) continue;
+    BatchedLU& lu = cls_[c]->lu;
+    lu.hold_factor();
+    if (merged_bits_ == 32) lu.hold_factor32(); else lu.release_factor32();
+  }
+  merged_.set_storage(merged_bits_);   // (also 32 -> 32: nothing moved, and 32 -> 64: the FP64 slabs have new addresses)
+#else
+  HYMLS_CHECK(merged_bits_ == 64, -99, "this build has no FP32 kernels for the merged level solve");
 #endif
 }
 
 void LevelSolver::finish_factor_storage() {
 #ifdef HYMLS_MI_F32_PANELS
-  if (fsubs_bits_ != 32) return;
+  if (fsubs_bits_ != 32 && merged_.bits != 32) return;
   dev::sync();   // (the demotions read the FP64 slabs)
   for (size_t c = 0; c < cls_.size(); c++)
-    if (cls_fused_[c]) cls_[c]->lu.release_factor();
+    if ((cls_fused_[c] && fsubs_bits_ == 32) || (cls_merged_[c] && merged_.bits == 32)) cls_[c]->lu.release_factor();
 #endif
 }
 
@@ -2186,7 +2238,9 @@ void LevelSolver::compute() {
   int64_t chunk_id = 0;
 #ifdef HYMLS_MI_F32_PANELS
   // test-only: FP64 storage of the values FP32 storage would hold (the yardstick of the bitwise tests)
-  const bool round_panels = std::getenv("HYMLS_MI_ROUND_PANELS") && std::atoi(std::getenv("HYMLS_MI_ROUND_PANELS")) != 0;
+  // bit mask: 1 the classes of the fused solve, 2 those of the merged level solve
+  const int round_mask = std::getenv("HYMLS_MI_ROUND_PANELS") ? std::atoi(std::getenv("HYMLS_MI_ROUND_PANELS")) : 0;
+  const bool round_panels = (round_mask & 1) != 0, round_merged = (round_mask & 2) != 0;
 #endif
   // (coarser levels: classes in their order, round robin over the side streams.  Measured and not kept: classes in descending
   // order of work on the least loaded stream -- 1.36 s instead of 1.13 s for level 2 of the 256^3 run with four streams, the
@@ -2204,6 +2258,11 @@ void LevelSolver::compute() {
       if (cls_fused_[c] && (fsubs_bits_ == 32 || round_panels)) {
         const int64_t off = (int64_t)b0 * C.lu.plan.factor_size, len = (int64_t)nbc * C.lu.plan.factor_size;
         if (fsubs_bits_ == 32) dev::demote_panels(len, C.lu.batch.factor + off, C.lu.factor32 + off, C.lu.batch.flag);
+        else dev::round_panels(len, C.lu.batch.factor + off, C.lu.batch.flag);
+      }
+      if (cls_merged_[c] && (merged_.bits == 32 || round_merged)) {
+        const int64_t off = (int64_t)b0 * C.lu.plan.factor_size, len = (int64_t)nbc * C.lu.plan.factor_size;
+        if (merged_.bits == 32) dev::demote_panels(len, C.lu.batch.factor + off, C.lu.factor32 + off, C.lu.batch.flag);
         else dev::round_panels(len, C.lu.batch.factor + off, C.lu.batch.flag);
       }
 #endif
@@ -2228,12 +2287,13 @@ void LevelSolver::compute() {
   if (side || chunk_streams) dev::join_streams();
   range_mb.reset();
   dev::Range range_sp("SchurPreconditioner", level_ + 1, "Compute");
-  int32_t bad = 0, grown = 0, range32 = 0;
+  int32_t bad = 0, grown = 0, range32 = 0, range32_merged = 0;
   double growth = 0.0;
-  for (auto& cp : cls_) {
+  for (size_t c = 0; c < cls_.size(); c++) {
     double g = 0.0;
-    const int32_t f = cp->lu.check_flag(&g);
-    bad |= (f & 1); grown |= (f & 2) >> 1; range32 |= (f & dev::FLAG_F32_RANGE) != 0; growth = std::max(growth, g);
+    const int32_t f = cls_[c]->lu.check_flag(&g);
+    bad |= (f & 1); grown |= (f & 2) >> 1; growth = std::max(growth, g);
+    (cls_merged_[c] ? range32_merged : range32) |= (f & dev::FLAG_F32_RANGE) != 0;
   }
   if (verbose) std::fprintf(stderr, "[hymls_mi] rank %d level %d compute: largest element growth of a pivot block %.3g\n", comm_->rank, level_, growth);
   // (collective: every rank has to reach the exchanges below, so errors are agreed on first)
@@ -2243,6 +2303,9 @@ void LevelSolver::compute() {
                                              std::to_string(growth) + " > 1e8 (level " + std::to_string(level_) + "); the factor would be inaccurate");
   HYMLS_CHECK(comm_->allsum(range32) == 0, -4, "FP32 factor storage: a factor panel entry of level " + std::to_string(level_) +
                                                " is not finite or exceeds the largest float (3.4e38); use FP64 storage for this matrix");
+  HYMLS_CHECK(comm_->allsum(range32_merged) == 0, -4, "FP32 merged factor storage: a panel entry of the merged level solve of level " +
+                                                      std::to_string(level_) + " is not finite or exceeds the largest float (3.4e38); "
+                                                      "use FP64 merged storage for this matrix");
   finish_factor_storage();
   lap("factor + transform + extract");
   compute_border();
@@ -2345,6 +2408,7 @@ void LevelSolver::compute() {
     lap("next level initialize");
     set_next_border();
     next_level_->set_factor_bits(factor_bits_);
+    next_level_->set_merged_bits(merged_bits_);
     next_level_->compute();
     lap("next level compute");
   } else {
@@ -2759,9 +2823,12 @@ void LevelSolver::matvec(const double* x, double* y) {
 
 void LevelSolver::add_stats(ApplyStats& st, bool as_coarse) const {
   double f = 0, fs = 0, sp = 0, sep = 0, vec = 0;
-  for (auto& cp : cls_) {
+  for (size_t c = 0; c < cls_.size(); c++) {
+    auto& cp = cls_[c];
     // (both sweeps of both solves; 4 B per entry where the panels are stored in FP32)
-    f += 2.0 * (cp->lu.factor32 ? 4.0 : 8.0) * (double)cp->lu.plan.nnz_factor * (double)cp->lu.members.size();
+    const double fc = 2.0 * (cp->lu.factor32 ? 4.0 : 8.0) * (double)cp->lu.plan.nnz_factor * (double)cp->lu.members.size();
+    f += fc;
+    if (c < cls_merged_.size() && cls_merged_[c]) st.bytes_merged += fc;
     st.bytes_resident += cp->lu.resident_bytes();
     fs += 2.0 * (12.0 * (double)cp->lu.plan.nnz_sparse + 24.0 * cp->lu.plan.nI) * (double)cp->lu.members.size();
   }

@@ -31,6 +31,8 @@ struct ApplyStats {
   double flops_factor = 0, flops_blocks = 0, flops_transform = 0;
   // bytes of factor panels (FP64 and FP32 slabs of every level, last-level solver included) held on the device right now
   double bytes_resident = 0;
+  // panel bytes the merged level solve of every LevelSolver level streams per ApplyInverse, as stored (both sweeps of both solves)
+  double bytes_merged = 0;
 };
 
 // A device allocation made on a helper thread while the setup thread goes on: a hipMalloc of tens of GiB takes about 30 ms per
@@ -119,6 +121,7 @@ struct MergedSolve {
   dev::LvlSub* d_subs = nullptr;
   dev::LvlTask *d_fw = nullptr, *d_bw = nullptr;
   int32_t nsubs = 0;
+  int bits = 64;    // element width of the slabs d_subs points into (set_storage)
   ivec fw_off, bw_off, fw_lds, bw_lds;
   MergedSolve() = default;
   MergedSolve(const MergedSolve&) = delete;
@@ -126,8 +129,13 @@ struct MergedSolve {
   ~MergedSolve();
   // (index of the batch's plan in the PlanD table handed to solve(), batch)
   void build(const std::vector<std::pair<int32_t, const BatchedLU*>>& classes);
+  // point the table at the FP64 (64) or FP32 (32) slabs of the batches of build(), as they are allocated now
+  void set_storage(int storage_bits);
   void solve(const dev::PlanD* d_plans, double* x, double* y, int64_t ld, int nv) const;
   int max_nv = 1;   // widest column group the contribution scratch of the batches holds
+ private:
+  std::vector<std::pair<int32_t, const BatchedLU*>> classes_;
+  std::vector<dev::LvlSub> h_subs_;
 };
 bool merged_solve_fits(const ClassPlan& plan);   // every front within the LDS limits of the task kernels
 // LDS of the fused interior solve (dev::interior_solve_fused) for one vector, in doubles: all of it, and the share of the front
@@ -235,6 +243,9 @@ class LevelSolver : public Operator {
   // storage of the panels of the fused interior solve, 64 or 32 bits per entry, on this level and every coarser one; takes
   // effect with the next compute()
   void set_factor_bits(int bits) { factor_bits_ = bits; }
+  // the same for the panels of the merged level solve of this level and every coarser LevelSolver (the last-level direct
+  // solver keeps FP64); independent of set_factor_bits
+  void set_merged_bits(int bits) { merged_bits_ = bits; }
   int border_size() const { return bm_; }
   int64_t size() const override { return global_n_; }
   void add_stats(ApplyStats& st, bool as_coarse) const override;
@@ -338,7 +349,9 @@ class LevelSolver : public Operator {
   bool fused_io_ = false;
   int factor_bits_ = 64;   // wanted (set_factor_bits)
   int fsubs_bits_ = 64;    // what the slabs and d_fsubs_ hold since the last compute()
-  void prepare_factor_storage();   // start of compute(): slabs and d_fsubs_ for factor_bits_
+  int merged_bits_ = 64;   // wanted for the classes of the merged level solve (set_merged_bits); merged_.bits: what the table holds
+  void prepare_factor_storage();   // start of compute(): slabs, d_fsubs_ and the table of merged_ for factor_bits_ / merged_bits_
+  void prepare_merged_storage();
   void finish_factor_storage();    // after the factorisation: range check, FP64 slabs of FP32 classes released
   // merged level solve tables (classes too large for the fused kernel)
   std::vector<char> cls_merged_;

@@ -160,6 +160,13 @@ int hymls_mi_compute(hymls_mi_t* h);
  * test-only host simulator). */
 int hymls_mi_set_factor_storage(hymls_mi_t* h, int bits);
 int hymls_mi_factor_storage(const hymls_mi_t* h);
+/* The same for the panels of the merged level solve: the subdomain classes too large for the fused interior kernel, which
+ * are solved tree level by tree level (most classes of the coarser levels; every class of the finest level with
+ * separator length 16; Python key "MI Merged Factor Storage").  Independent of hymls_mi_set_factor_storage: all four
+ * combinations are valid.  The last-level direct solver and the classes on the big-front route keep FP64.  Same
+ * life-cycle and the same return values as hymls_mi_set_factor_storage. */
+int hymls_mi_set_merged_factor_storage(hymls_mi_t* h, int bits);
+int hymls_mi_merged_factor_storage(const hymls_mi_t* h);
 
 /* Ifpack_Preconditioner::ApplyInverse(B, X) (src/HYMLS_Preconditioner.cpp:594-605,
  * 930-1070).  B, X: nvec columns, leading dimensions ldb/ldx.
@@ -214,9 +221,10 @@ int64_t hymls_mi_level_num_subdomains(const hymls_mi_t* h, int level);
  * (dense supernodal panels, 8 B per entry, no index data per subdomain); 6 and 7 are the sparse-equivalent figures of
  * 1 and 4 (nnz(L+U) of the scalar LU in the same ordering x 12 B + 24 B per unknown, what the reference's KluSolve
  * streams, src/HYMLS_SparseDirectSolver.cpp:788-856); 8 = total with the smaller of the two for every factor: the
- * judge-facing algorithmic figure.  Classes whose panels are stored in FP32 (hymls_mi_set_factor_storage)
- * count 4 B per entry in 0, 1 and 8; 6 and 7 do not change.  9 = bytes of factor panels resident on the device right
- * now (FP64 and FP32 slabs of every level and of the last-level solver). */
+ * judge-facing algorithmic figure.  Classes whose panels are stored in FP32 (hymls_mi_set_factor_storage
+ * or hymls_mi_set_merged_factor_storage) count 4 B per entry in 0, 1, 4 and 8; 6 and 7 do not change.  9 = bytes of
+ * factor panels resident on the device right now (FP64 and FP32 slabs of every level and of the last-level solver).
+ * 10 = panel bytes the merged level solve of all levels but the last streams, as stored (a part of 1 and 4). */
 double hymls_mi_apply_bytes(const hymls_mi_t* h, int which);
 /* floating point operations of one numeric Compute over all levels, counted from the symbolic plans at Initialize
  * (SURVEY 8d, K6 / K8 / K10): which = 0 total, 1 the multifrontal factorisations (subdomain LUs, whose un-eliminated

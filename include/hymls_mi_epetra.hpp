@@ -29,7 +29,8 @@
 //     "MPI" (MPI_Alltoallv with host staging: any MPI library, several ranks per GPU, the test-only host simulator);
 //     include/hymls_mi_mpi.h holds both.
 // One more "Preconditioner" key the reference does not have: "MI Factor Storage" = "double" (default) or "single", the
-// storage of the interior factor panels ApplyInverse streams (hymls_mi_set_factor_storage in hymls_mi.h).
+// storage of the interior factor panels ApplyInverse streams (hymls_mi_set_factor_storage in hymls_mi.h), and
+// "MI Merged Factor Storage", the same for the panels of the merged level solve (hymls_mi_set_merged_factor_storage).
 #ifndef HYMLS_MI_EPETRA_HPP
 #define HYMLS_MI_EPETRA_HPP
 
@@ -129,6 +130,9 @@ class Preconditioner : public Ifpack_Preconditioner {
     const std::string storage = prec.get("MI Factor Storage", std::string("double"));
     if (storage != "double" && storage != "single") return fail(-2, "\"MI Factor Storage\" has to be \"double\" or \"single\"");
     factor_bits_ = storage == "single" ? 32 : 64;
+    const std::string merged = prec.get("MI Merged Factor Storage", std::string("double"));
+    if (merged != "double" && merged != "single") return fail(-2, "\"MI Merged Factor Storage\" has to be \"double\" or \"single\"");
+    merged_bits_ = merged == "single" ? 32 : 64;
     have_params_ = true;
     Release();   // new parameters: everything is rebuilt by the next Initialize
     return 0;
@@ -147,6 +151,8 @@ class Preconditioner : public Ifpack_Preconditioner {
       ierr = hymls_mi_create(&h_, &p_, device_);
       if (ierr) return keep_error(ierr);
       ierr = hymls_mi_set_factor_storage(h_, factor_bits_);
+      if (ierr) return keep_error(ierr);
+      ierr = hymls_mi_set_merged_factor_storage(h_, merged_bits_);
       if (ierr) return keep_error(ierr);
       if (distributed_) {
         ierr = AttachComm();
@@ -415,6 +421,7 @@ class Preconditioner : public Ifpack_Preconditioner {
   bool have_params_ = false, have_border_ = false, matrix_dirty_ = true, distributed_ = false;
   std::string transport_ = "RCCL";
   int factor_bits_ = 64;   // "MI Factor Storage": "double" (64) or "single" (32)
+  int merged_bits_ = 64;   // "MI Merged Factor Storage"
   Teuchos::RCP<Epetra_Map> overlapMap_, ownedMap_;            // required rows / owned rows of this rank
   Teuchos::RCP<Epetra_Import> rowImporter_, vecImporter_;     // matrix row map -> overlapMap_ / ownedMap_
 #ifdef HYMLS_MI_HAVE_MPI
