@@ -17,10 +17,10 @@ def __getattr__(name):
     if name in ("Solver", "BorderedSolver"):
         from . import solver
         return getattr(solver, name)
-    if name == "NativeSolver":
+    if name in ("NativeSolver", "NativeBorderedSolver"):
         from . import native_solver
-        return native_solver.NativeSolver
+        return getattr(native_solver, name)
     raise AttributeError("module 'hymls_amd' has no attribute %r" % name)
 
-__all__ = ["Solver", "BorderedSolver", "NativeSolver", "Preconditioner", "HymlsError", "load_library", "generate_matrix", "generate_testvector", "generate_rows",
+__all__ = ["Solver", "BorderedSolver", "NativeSolver", "NativeBorderedSolver", "Preconditioner", "HymlsError", "load_library", "generate_matrix", "generate_testvector", "generate_rows",
            "generate_testvector_rows", "generate_problem", "LIB_PATH"]

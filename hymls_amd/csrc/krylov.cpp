@@ -13,6 +13,13 @@
 // every other vector and every sum stays FP64.  Column k is widened into t for ApplyInverse and K x, the three passes
 // orthogonalise the FP64 w in place against the float columns, and w / ||w|| is formed in FP64 and rounded once into
 // column k + 1.  A cycle ends early at KRY_F32_CYCLE_THETA, and only an explicitly computed residual ends the solve.
+//
+// Bordered systems [K V; W' C] [x; s] = [b; t] (hymls_mi_solver_solve_bordered, the reference's HYMLS::BorderedSolver):
+// the Krylov vectors are the augmented vectors of n + m entries with the border scalars in the tail of the same device
+// array, so every launcher above runs on n + m rows and the inner product is that of the reference's BorderedVector.  Only
+// the two hooks differ: the operator is K x followed by dev::kry_border_product (under HYMLS_MI_BORDERED_SOLVER: the
+// test-only simulators without that launcher leave the macro out and the entry returns -99), the preconditioner is
+// LevelSolver::apply_inverse_bordered with T read from and S written to the tail.  One GPU.
 #include "../../include/hymls_mi_solver.h"
 #include "capi_internal.hpp"
 #include "krylov.hpp"
@@ -46,6 +53,7 @@ struct hymls_mi_solver {
   double* V = nullptr;             // [(m + 1) * ld]; FP32 storage: the same allocation holds float[(m + 1) * ld]
   double* vec = nullptr;           // 7 vectors of ld: x, r, w, t, p, prev, staged b
   double* work = nullptr;          // reduction scratch (dev::KryWork)
+  double* bc = nullptr;            // bordered solves: the device copy of C (HYMLS_MI_SOLVER_MAX_BORDER^2 doubles)
   dev::KryWork ws{};
   bool have_prev = false;
   bool profiling = false;
@@ -62,10 +70,34 @@ struct Run {
   int64_t n, ld;
   bool dist;
   double *x, *r, *w, *t, *p, *prev, *bst;
+  // bordered solve (bm > 0): n counts the augmented rows, nh of them are the rows of K and the last bm the border scalars
+  int64_t nh = 0;
+  int bm = 0;
+  const double* dC = nullptr;      // device copy of C
+  std::vector<double> bt, bs;      // host T and S of one bordered ApplyInverse
 
   void mark(int phase, bool begin) { if (s->profiling) dev::kry_mark(s->timer, phase, begin); }
-  void prec(const double* in, double* out) { mark(1, true); L->apply_inverse_mv(in, n, out, n, 1); mark(1, false); }
-  void matvec(const double* in, double* out) { mark(2, true); L->matvec(in, out); mark(2, false); }
+  // the two hooks of the iteration; with a border: M^{-1} [in; T] = [out; S] with T and S in the tails, and
+  // [K V; W' C] in = K in(0:nh) followed by the border product
+  void prec(const double* in, double* out) {
+    mark(1, true);
+    if (bm == 0) {
+      L->apply_inverse_mv(in, n, out, n, 1);
+    } else {
+      dev::d2h(bt.data(), in + nh, bm * sizeof(double));
+      L->apply_inverse_bordered(in, bt.data(), out, bs.data());
+      dev::h2d(out + nh, bs.data(), bm * sizeof(double));
+    }
+    mark(1, false);
+  }
+  void matvec(const double* in, double* out) {
+    mark(2, true);
+    L->matvec(in, out);
+#ifdef HYMLS_MI_BORDERED_SOLVER
+    if (bm > 0) dev::kry_border_product(nh, bm, L->border_v(), nh, L->border_w(), nh, dC, in, out, s->ws);
+#endif
+    mark(2, false);
+  }
 
   double allsum(double v) {
     if (!dist) return v;
@@ -270,8 +302,8 @@ void check_params(const hymls_mi_solver_params& p) {
 }
 
 void free_buffers(hymls_mi_solver* s) {
-  dev::free(s->V); dev::free(s->vec); dev::free(s->work);
-  s->V = s->vec = s->work = nullptr;
+  dev::free(s->V); dev::free(s->vec); dev::free(s->work); dev::free(s->bc);
+  s->V = s->vec = s->work = s->bc = nullptr;
   s->n = s->ld = 0; s->m_alloc = 0; s->have_prev = false;
 }
 
@@ -328,17 +360,18 @@ int hymls_mi_solver_set_tolerance(hymls_mi_solver_t* s, double tol) {
   return 0;
 }
 
-int hymls_mi_solver_solve(hymls_mi_solver_t* s, const double* B, int64_t ldb, double* X, int64_t ldx, int nvec, int on_device) {
-  if (!s) return -2;
+}  // extern "C"
+
+namespace {
+// The columns of one solve call on a computed handle.  bm = 0: K X(:, c) = B(:, c), c < nvec.  bm > 0 (the border of the
+// handle, nvec = 1): the augmented system; B and X hold the nh rows of K, T and S (host, bm values, either may be null)
+// the border part.  Returns 0, or -1 when a column did not reach the tolerance; errors are thrown.
+int solve_columns(hymls_mi_solver* s, const HandleView& hv_, int bm, const double* B, int64_t ldb, const double* T, double* X,
+                  int64_t ldx, double* S, int nvec, int on_device) {
   int status = 0;
-  SOLVER_BEGIN
-  HYMLS_CHECK(hv_.computed && hv_.top, -1, "The preconditioner has not yet been computed.");
-  HYMLS_CHECK(hv_.top->border_size() == 0, -2, "the native solver does not solve bordered systems");
-  HYMLS_CHECK(nvec >= 0 && (nvec == 0 || (B && X)), -2, "solve: null B or X");
-  check_params(s->p);
   LevelSolver* L = hv_.top;
-  const int64_t n = L->num_owned();
-  HYMLS_CHECK(nvec <= 1 || (ldb >= n && ldx >= n), -2, "solve: leading dimension smaller than the number of rows");
+  const int64_t nh = L->num_owned();
+  const int64_t n = nh + bm;       // rows of the Krylov vectors
   const bool gm = s->p.method == 0;
   const int m = gm ? std::min(s->p.num_blocks, std::max(s->p.max_iters, 1)) : 0;
   // buffers: grown when the problem or the restart length grows; the "Previous" solution survives only if n is unchanged
@@ -364,6 +397,15 @@ int hymls_mi_solver_solve(hymls_mi_solver_t* s, const double* B, int64_t ldb, do
     s->bits_alloc = s->basis_bits;
   }
   Run R{s, L, hv_.comm, n, s->ld, hv_.comm->distributed()};
+  R.nh = nh;
+  if (bm > 0) {
+    if (!s->bc) s->bc = (double*)dev::alloc((size_t)HYMLS_MI_SOLVER_MAX_BORDER * HYMLS_MI_SOLVER_MAX_BORDER * sizeof(double));
+    dev::h2d(s->bc, L->border_c(), (size_t)bm * bm * sizeof(double));
+    R.bm = bm;
+    R.dC = s->bc;
+    R.bt.assign(bm, 0.0);
+    R.bs.assign(bm, 0.0);
+  }
   double* v = s->vec;
   R.x = v; R.r = v + s->ld; R.w = v + 2 * s->ld; R.t = v + 3 * s->ld; R.p = v + 4 * s->ld;
   R.prev = v + 5 * s->ld; R.bst = v + 6 * s->ld;
@@ -372,20 +414,39 @@ int hymls_mi_solver_solve(hymls_mi_solver_t* s, const double* B, int64_t ldb, do
     const ivec& gids = L->owned_gids();
     rnd.resize(n);
     for (int64_t i = 0; i < n; i++) {
-      const uint64_t u = splitmix64(s->p.seed ^ splitmix64((uint64_t)gids[i]));
+      // (border scalar j: the global row id that follows the rows of K)
+      const uint64_t u = splitmix64(s->p.seed ^ splitmix64(i < nh ? (uint64_t)gids[i] : (uint64_t)(L->size() + (i - nh))));
       rnd[i] = (double)(u >> 11) * (1.0 / 9007199254740992.0) * 2.0 - 1.0;
     }
   }
   for (int c = 0; c < nvec; c++) {
     const double* b = B + (int64_t)c * ldb;
-    if (!on_device) { dev::h2d(R.bst, b, n * sizeof(double)); b = R.bst; }
+    if (bm > 0) {                // the augmented right-hand side [b; t] is always staged
+      if (on_device) dev::d2d(R.bst, b, nh * sizeof(double));
+      else dev::h2d(R.bst, b, nh * sizeof(double));
+      if (T) dev::h2d(R.bst + nh, T, bm * sizeof(double));
+      else dev::zero(R.bst + nh, bm * sizeof(double));
+      b = R.bst;
+    } else if (!on_device) { dev::h2d(R.bst, b, n * sizeof(double)); b = R.bst; }
     if (s->p.initial_vector == 1) dev::h2d(R.x, rnd.data(), n * sizeof(double));
     else if (s->p.initial_vector == 2 && s->have_prev) dev::d2d(R.x, R.prev, n * sizeof(double));
     else dev::zero(R.x, n * sizeof(double));
     R.mark(0, true);
     int its = 0, restarts = 0;
     double rel = 0;
-    if (!gm) R.cg(b, its, rel);
+    bool solved = false;
+    if (bm > 0 && s->p.initial_vector == 2 && s->have_prev) {
+      // bordered solve from the "Previous" solution: if that vector already solves this system to the tolerance, measured
+      // as the true residual over the right-hand side (what a "Zero" start measures), there is nothing to iterate.
+      // Otherwise the iteration runs as ever, relative to its own first residual
+      const double nrm_b = R.norm(b);
+      R.matvec(R.x, R.t);
+      R.mark(3, true); dev::kry_sub(n, b, R.t, R.r); R.mark(3, false);
+      const double nrm_r = R.norm(R.r);
+      if (nrm_r <= s->p.tol * nrm_b) { rel = nrm_b > 0.0 ? nrm_r / nrm_b : 0.0; solved = true; }
+    }
+    if (solved) {}
+    else if (!gm) R.cg(b, its, rel);
 #ifdef HYMLS_MI_F32_BASIS
     else if (s->basis_bits == 32) R.gmres<float>(b, its, rel, restarts);
 #endif
@@ -396,8 +457,9 @@ int hymls_mi_solver_solve(hymls_mi_solver_t* s, const double* B, int64_t ldb, do
     s->achieved = rel;
     dev::d2d(R.prev, R.x, n * sizeof(double));
     s->have_prev = true;
-    if (on_device) dev::d2d(X + (int64_t)c * ldx, R.x, n * sizeof(double));
-    else dev::d2h(X + (int64_t)c * ldx, R.x, n * sizeof(double));
+    if (on_device) dev::d2d(X + (int64_t)c * ldx, R.x, nh * sizeof(double));
+    else dev::d2h(X + (int64_t)c * ldx, R.x, nh * sizeof(double));
+    if (bm > 0 && S) dev::d2h(S, R.x + nh, bm * sizeof(double));
     if (!(rel <= s->p.tol)) status = -1;
   }
   if (s->profiling) dev::kry_collect(s->timer, s->secs);
@@ -407,6 +469,49 @@ int hymls_mi_solver_solve(hymls_mi_solver_t* s, const double* B, int64_t ldb, do
     std::snprintf(buf, sizeof buf, "Krylov solver did not converge: %d iterations, relative residual %.3e", s->its, s->achieved);
     s->err = buf;
   }
+  return status;
+}
+}  // namespace
+
+extern "C" {
+
+int hymls_mi_solver_solve(hymls_mi_solver_t* s, const double* B, int64_t ldb, double* X, int64_t ldx, int nvec, int on_device) {
+  if (!s) return -2;
+  int status = 0;
+  SOLVER_BEGIN
+  HYMLS_CHECK(hv_.computed && hv_.top, -1, "The preconditioner has not yet been computed.");
+  HYMLS_CHECK(hv_.top->border_size() == 0, -2, "the native solver does not solve bordered systems");
+  HYMLS_CHECK(nvec >= 0 && (nvec == 0 || (B && X)), -2, "solve: null B or X");
+  check_params(s->p);
+  const int64_t n = hv_.top->num_owned();
+  HYMLS_CHECK(nvec <= 1 || (ldb >= n && ldx >= n), -2, "solve: leading dimension smaller than the number of rows");
+  status = solve_columns(s, hv_, 0, B, ldb, nullptr, X, ldx, nullptr, nvec, on_device);
+  SOLVER_END
+  return status;
+}
+
+int hymls_mi_solver_solve_bordered(hymls_mi_solver_t* s, const double* B, const double* T, double* X, double* S, int on_device) {
+  if (!s) return -2;
+  int status = 0;
+  SOLVER_BEGIN
+#ifndef HYMLS_MI_BORDERED_SOLVER
+  (void)B; (void)T; (void)X; (void)S; (void)on_device; (void)status;
+  throw hymls::Error(-99, "this build has no border product kernel (a test-only simulator without it)");
+#else
+  HYMLS_CHECK(hv_.computed && hv_.top, -1, "The preconditioner has not yet been computed.");
+  HYMLS_CHECK(!hv_.comm->distributed(), -99, "solve_bordered: one GPU only (sharded handles are not supported)");
+  HYMLS_CHECK(B && X, -2, "solve_bordered: null B or X");
+  check_params(s->p);
+  const int bm = hv_.top->border_size();
+  const int64_t n = hv_.top->num_owned();
+  if (bm == 0) {
+    status = solve_columns(s, hv_, 0, B, n, nullptr, X, n, nullptr, 1, on_device);
+  } else {
+    HYMLS_CHECK(bm <= HYMLS_MI_SOLVER_MAX_BORDER, -2, "solve_bordered: at most 32 border columns");
+    HYMLS_CHECK(s->p.method == 0, -99, "solve_bordered: the bordered operator is indefinite, CG does not apply (use GMRES)");
+    status = solve_columns(s, hv_, bm, B, n, T, X, n, S, 1, on_device);
+  }
+#endif
   SOLVER_END
   return status;
 }
@@ -504,6 +609,35 @@ int hymls_mi_orthogonalize_f32(hymls_mi_t* h, int64_t n, int32_t k, const float*
     dev::free(work);
     std::copy(hk.begin(), hk.begin() + k, hcoef);
     *wnorm = hk[k];
+#endif
+  } catch (const hymls::Error& e) { *hv.err = e.what(); return e.code; }
+  catch (const std::exception& e) { *hv.err = e.what(); return -3; }
+  return 0;
+}
+
+int hymls_mi_border_product(hymls_mi_t* h, int64_t n, int32_t m, const double* V, int64_t ldv, const double* W, int64_t ldw,
+                            const double* C, const double* z, double* y) {
+  if (!h) return -2;
+  HandleView hv = handle_view(h);
+  try {
+#ifndef HYMLS_MI_BORDERED_SOLVER
+    (void)n; (void)m; (void)V; (void)ldv; (void)W; (void)ldw; (void)C; (void)z; (void)y;
+    throw hymls::Error(-99, "this build has no border product kernel (a test-only simulator without it)");
+#else
+    dev::bind(hv.ctx);
+    HYMLS_CHECK(n >= 1 && m >= 1 && m <= HYMLS_MI_SOLVER_MAX_BORDER && ldv >= n && ldw >= n && V && W && z && y && z != y, -2,
+                "border_product: need n >= 1, 1 <= m <= 32, ldv and ldw >= n and non-null, distinct arrays");
+    const int nb = dev::kry_row_grid(n);
+    double* work = (double*)dev::alloc(((size_t)nb * m + (size_t)m * m) * sizeof(double));
+    dev::KryWork ws{};
+    ws.part = work;
+    double* dC = nullptr;
+    try {
+      if (C) { dC = work + (size_t)nb * m; dev::h2d(dC, C, (size_t)m * m * sizeof(double)); }
+      dev::kry_border_product(n, m, V, ldv, W, ldw, dC, z, y, ws);
+      dev::sync();
+    } catch (...) { dev::free(work); throw; }
+    dev::free(work);
 #endif
   } catch (const hymls::Error& e) { *hv.err = e.what(); return e.code; }
   catch (const std::exception& e) { *hv.err = e.what(); return -3; }

@@ -86,6 +86,21 @@ void kry_round_div(int64_t n, const double* x, double s, float* y);
 // y <- (float)(x / *d) where *d > 0, else (float) x (device scalar): the new column, normalised in FP64 and rounded once
 void kry_round_scale_by(int64_t n, const double* x, const double* d, float* y);
 
+// ---- bordered systems [K V; W' C] on the augmented vectors z = [x; s], y (n + m entries each, the border scalars in the
+// tail [n, n + m) of the same device array; z and y must not overlap):
+//   y[0:n) += V s            (after K x has been written to y[0:n)); per row the sum over j ascending, then one add
+//   y[n + j] = W(:, j)' x + sum_l C[j + m l] s_l     (l ascending, added to the finished W' x)
+// V, W: n x m column-major device arrays (leading dimensions ldv, ldw >= n), dC: device copy of C or nullptr (zero),
+// 1 <= m <= KRY_BORDER_MAX.  The columns are handled KRY_BORDER_CHUNK at a time, one pass over the rows of kry_row_grid(n)
+// workgroups per chunk (m <= 8: V, W, x and y are read once, (2 m + 3) n 8 bytes); the W' x partials of every workgroup go
+// to ws.part[workgroup * m + j], and one workgroup sums them in the fixed order of the other reductions and writes the
+// tail.  Implemented by krylov_hip.hip and by the test-only tests/krylov_border_sim; krylov.cpp refers to it only under
+// HYMLS_MI_BORDERED_SOLVER, because the other simulators have none.
+constexpr int KRY_BORDER_MAX = 32;
+constexpr int KRY_BORDER_CHUNK = 8;
+void kry_border_product(int64_t n, int32_t m, const double* V, int64_t ldv, const double* W, int64_t ldw, const double* dC,
+                        const double* z, double* y, const KryWork& ws);
+
 // phase timing of a solve: events recorded on the stream (the simulator takes host clock readings)
 struct KryTimer;
 KryTimer* kry_timer_create();

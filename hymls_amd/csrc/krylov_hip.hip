@@ -11,6 +11,7 @@
 //   k_kry_rows<false>   x += V y (solution update), the same kernel without the norm
 //   k_kry_reduce*       stage two of every reduction: the partials of one column summed by one workgroup in a fixed
 //                       tree, on the device, so h1 feeds pass B and h2 pass C without a host round trip
+//   k_kry_border_*      the border product of a bordered system [K V; W' C] behind K x: y += V s and the tail W' x + C s
 // plus the vector passes of GMRES and CG.  No atomics anywhere: every result is bitwise reproducible.
 //
 // k_kry_tile and k_kry_rows take the element type of the basis.  With float ("MI Basis Storage" = single) a basis entry
@@ -210,6 +211,63 @@ __global__ void __launch_bounds__(256) k_kry_cg_p(int64_t n, double beta, const 
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = z[i] + beta * p[i];
 }
 
+// ---- bordered operator (krylov.hpp: kry_border_product).  Stage one, MC <= KRY_BORDER_CHUNK columns [c0, c0 + MC) of the
+// border: one row per thread, the MC coalesced column reads of V and of W; y[i] += sum_j V[i, j] s_j (j ascending) and the
+// thread's partials of W(:, j)' x in registers, summed per workgroup in the fixed tree into part[workgroup * m + c0 + j]
+template <int MC>
+__global__ void __launch_bounds__(256) k_kry_border_rows(int64_t n, int m, int c0, const double* __restrict__ V, int64_t ldv,
+                                                         const double* __restrict__ W, int64_t ldw,
+                                                         const double* __restrict__ z, double* __restrict__ y,
+                                                         double* __restrict__ part) {
+  __shared__ double red[MC][256];
+  const int t = threadIdx.x;
+  const double* Vc = V + (int64_t)c0 * ldv;
+  const double* Wc = W + (int64_t)c0 * ldw;
+  double s[MC], acc[MC];
+#pragma unroll
+  for (int j = 0; j < MC; j++) { s[j] = z[n + c0 + j]; acc[j] = 0.0; }   // the border scalars: the tail of z, on the device
+  for (int64_t i = (int64_t)blockIdx.x * 256 + t; i < n; i += (int64_t)gridDim.x * 256) {
+    const double xi = z[i];
+    double sv = 0.0;
+#pragma unroll
+    for (int j = 0; j < MC; j++) {
+      sv += Vc[(int64_t)j * ldv + i] * s[j];
+      acc[j] += Wc[(int64_t)j * ldw + i] * xi;
+    }
+    y[i] = y[i] + sv;
+  }
+#pragma unroll
+  for (int j = 0; j < MC; j++) red[j][t] = acc[j];
+  for (int st = 128; st > 0; st >>= 1) {   // block_sum256 for the MC columns at once
+    __syncthreads();
+    if (t < st) {
+#pragma unroll
+      for (int j = 0; j < MC; j++) red[j][t] += red[j][t + st];
+    }
+  }
+  __syncthreads();
+  if (t < MC) part[(int64_t)blockIdx.x * m + c0 + t] = red[t][0];
+}
+// stage two, one workgroup: y[n + j] = (the nb partials of column j, summed as k_kry_reduce does) + sum_l C[j + m l] s_l
+__global__ void __launch_bounds__(256) k_kry_border_tail(const double* __restrict__ part, int nb, int64_t n, int m,
+                                                         const double* __restrict__ dC, const double* __restrict__ z,
+                                                         double* __restrict__ y) {
+  __shared__ double red[256];
+  const int t = threadIdx.x;
+  for (int j = 0; j < m; j++) {
+    double s = 0.0;
+    for (int b = t; b < nb; b += 256) s += part[(int64_t)b * m + j];
+    red[t] = s;
+    block_sum256(red);
+    if (t == 0) {
+      double v = red[0];
+      if (dC)
+        for (int l = 0; l < m; l++) v += dC[j + (int64_t)m * l] * z[n + l];
+      y[n + j] = v;
+    }
+  }
+}
+
 static inline void kcheck() { KRY_CHECK(hipGetLastError()); }
 
 template <bool UPD, class BT>
@@ -318,6 +376,32 @@ void kry_cg_xr(int64_t n, double alpha, const double* p, const double* q, double
 }
 void kry_cg_p(int64_t n, double beta, const double* z, double* p) {
   hipLaunchKernelGGL(k_kry_cg_p, dim3(vec_grid(n)), dim3(256), 0, kstream(), n, beta, z, p);
+  kcheck();
+}
+
+template <int MC>
+static void border_rows(int nb, int64_t n, int32_t m, int c0, const double* V, int64_t ldv, const double* W, int64_t ldw,
+                        const double* z, double* y, const KryWork& ws) {
+  hipLaunchKernelGGL((k_kry_border_rows<MC>), dim3(nb), dim3(256), 0, kstream(), n, m, c0, V, ldv, W, ldw, z, y, ws.part);
+  kcheck();
+}
+void kry_border_product(int64_t n, int32_t m, const double* V, int64_t ldv, const double* W, int64_t ldw, const double* dC,
+                        const double* z, double* y, const KryWork& ws) {
+  if (n < 1 || m < 1 || m > KRY_BORDER_MAX || ldv < n || ldw < n) throw Error(-2, "border product: n >= 1, 1 <= m <= 32, ldv, ldw >= n");
+  const int nb = kry_row_grid(n);
+  for (int c0 = 0; c0 < m; c0 += KRY_BORDER_CHUNK) {
+    switch (std::min(KRY_BORDER_CHUNK, m - c0)) {
+      case 1: border_rows<1>(nb, n, m, c0, V, ldv, W, ldw, z, y, ws); break;
+      case 2: border_rows<2>(nb, n, m, c0, V, ldv, W, ldw, z, y, ws); break;
+      case 3: border_rows<3>(nb, n, m, c0, V, ldv, W, ldw, z, y, ws); break;
+      case 4: border_rows<4>(nb, n, m, c0, V, ldv, W, ldw, z, y, ws); break;
+      case 5: border_rows<5>(nb, n, m, c0, V, ldv, W, ldw, z, y, ws); break;
+      case 6: border_rows<6>(nb, n, m, c0, V, ldv, W, ldw, z, y, ws); break;
+      case 7: border_rows<7>(nb, n, m, c0, V, ldv, W, ldw, z, y, ws); break;
+      default: border_rows<8>(nb, n, m, c0, V, ldv, W, ldw, z, y, ws); break;
+    }
+  }
+  hipLaunchKernelGGL(k_kry_border_tail, dim3(1), dim3(256), 0, kstream(), ws.part, nb, n, m, dC, z, y);
   kcheck();
 }
 

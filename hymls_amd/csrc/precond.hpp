@@ -247,6 +247,11 @@ class LevelSolver : public Operator {
   // solver keeps FP64); independent of set_factor_bits
   void set_merged_bits(int bits) { merged_bits_ = bits; }
   int border_size() const { return bm_; }
+  // the border as set_border took it (read-only, for the bordered operator of the native Krylov solver): V and W in the
+  // layout of apply_inverse, num_owned() x border_size() column-major on the device, C border_size()^2 on the host
+  const double* border_v() const { return d_bVu_; }
+  const double* border_w() const { return d_bWu_; }
+  const double* border_c() const { return bC_.data(); }
   int64_t size() const override { return global_n_; }
   void add_stats(ApplyStats& st, bool as_coarse) const override;
   // y = K x on the rows this rank owns (vectors in the layout of apply_inverse); sharded: collective, the values

@@ -17,6 +17,8 @@ hymls_amd.Preconditioner and hymls_amd.Solver, so that the reference's own examp
   1 / sqrt(number of cells) (create_nullspace, src/HYMLS_MainUtils.cpp:361-376); the exact solution of a generated
   right-hand side has the null space projected out (src/main.cpp:401-409).
 * "x-periodic" / "y-periodic" / "z-periodic" of the "Problem" list (generated Stokes-C matrices).
+* "MI Native Solver" (bool, "Solver" list, default false): the Krylov loop of the library itself
+  (hymls_amd.NativeSolver / NativeBorderedSolver) instead of the torch classes.
 Not supported: "Null Space Type" = "File" / "Checkerboard", deflation of further vectors, eigenvalue runs.
 """
 import os
@@ -140,11 +142,15 @@ def run(xml_file, *overlays, lib=None, device=None, out=sys.stdout):
         V = np.zeros((n, dof))
         for d in range(dof):
             V[d::dof, d] = 1.0 / np.sqrt(n // dof)
-    if V is not None:
+    native = bool(params.get("Solver", {}).get("MI Native Solver", False))
+    if V is not None and native:
+        S = hymls_amd.NativeBorderedSolver(P, params)
+        S.SetBorder(V)
+    elif V is not None:
         S = hymls_amd.BorderedSolver(P, P, params)
         S.SetBorder(V, device=device)
     elif null_space == "None":
-        S = hymls_amd.Solver(P, P, params)
+        S = hymls_amd.NativeSolver(P, params) if native else hymls_amd.Solver(P, P, params)
     else:
         raise ValueError("Null Space Type '%s' is not supported" % null_space)
     rng = np.random.default_rng(drv.get("Random Seed", 1234) if drv.get("Random Seed", -1) != -1 else 1234)

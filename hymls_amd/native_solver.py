@@ -5,6 +5,10 @@ the reference's ``HYMLS::BaseSolver``) that lives in the library itself, next to
 has the same methods; K is the matrix of the computed preconditioner P and the preconditioner is P's ApplyInverse.
 The solver symbols are bound from ``P._lib`` when the first NativeSolver is made, so libraries without them still
 load through ``hymls_amd.load_library``.
+
+``NativeBorderedSolver(P, params)`` is the native counterpart of ``hymls_amd.BorderedSolver``: the bordered system
+[K V; W' C] [x; s] = [b; t] with the border of P (hymls_mi_solver_solve_bordered).  Its two symbols are bound from a table
+of their own when the first NativeBorderedSolver or ``border_product`` is used.
 """
 import ctypes as C
 
@@ -42,6 +46,25 @@ _SIG = {
     "hymls_mi_solver_last_error": (C.c_char_p, [C.c_void_p]),
     "hymls_mi_solver_destroy": (None, [C.c_void_p]),
 }
+
+
+# bound apart from _SIG (bind_bordered): a library may have the solver without the bordered entries
+_SIG_BORDERED = {
+    "hymls_mi_solver_solve_bordered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "hymls_mi_border_product": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
+def bind_bordered(lib):
+    """declare the two bordered symbols on a loaded library (once); AttributeError if it lacks one"""
+    if not getattr(lib, "_hymls_bordered_bound", False):
+        for name, (res, args) in _SIG_BORDERED.items():
+            f = getattr(lib, name)
+            f.restype = res
+            f.argtypes = args
+        lib._hymls_bordered_bound = True
+    return lib
 
 
 def bind_solver(lib):
@@ -182,6 +205,66 @@ class NativeSolver:
             self.close()
         except Exception:
             pass
+
+
+class NativeBorderedSolver(NativeSolver):
+    """[K V; W' C] [x; s] = [b; t] with the library's own GMRES on the augmented vectors [x; s] (the interface of
+    hymls_amd.BorderedSolver); the border is the one of P, for the operator and for the preconditioner.  One GPU."""
+
+    def __init__(self, P, params=None):
+        super().__init__(P, params)
+        bind_bordered(self._lib)
+
+    def SetBorder(self, V, W=None, C=None):
+        """sets the border of P; call P.Compute() afterwards (as in the reference).  V=None removes it."""
+        return self._P.SetBorder(V, W, C)
+
+    def ApplyInverse(self, B, T=None, X=None, S=None):
+        """returns (X, S).  B: torch tensor on the device or numpy array, (n,) float64; T: array-like (m,), default 0.
+        X (same kind as B) and S (numpy, (m,)) may be given to receive the result.  Raises RuntimeError if the tolerance
+        was not reached (X and S, where given, then hold the last iterate).  Without a border: the plain solve, S empty."""
+        n, m = self._P._n, getattr(self._P, "_m", 0)
+        Tc = None if T is None or m == 0 else np.ascontiguousarray(np.asarray(T, dtype=np.float64).reshape(m))
+        Sc = np.zeros(m)
+        tp, sp = (Tc.ctypes.data if Tc is not None else None), (Sc.ctypes.data if m else None)
+        if hasattr(B, "data_ptr"):
+            import torch
+            assert B.dtype == torch.float64 and B.is_contiguous() and B.dim() == 1 and B.shape[0] == n
+            if X is None:
+                X = torch.empty_like(B)
+            assert X.is_contiguous() and X.shape == B.shape and X.dtype == torch.float64
+            ierr = self._lib.hymls_mi_solver_solve_bordered(self._s, B.data_ptr(), tp, X.data_ptr(), sp, 1)
+            out = X
+        else:
+            Bc = np.ascontiguousarray(np.asarray(B, dtype=np.float64))
+            assert Bc.shape == (n,)
+            Xc = np.empty_like(Bc)
+            ierr = self._lib.hymls_mi_solver_solve_bordered(self._s, Bc.ctypes.data, tp, Xc.ctypes.data, sp, 0)
+            if X is not None and ierr in (0, -1):
+                X[...] = Xc
+                out = X
+            else:
+                out = Xc
+        if S is not None and ierr in (0, -1):
+            S[...] = Sc
+            Sc = S
+        if ierr == -1:
+            raise RuntimeError(self._lib.hymls_mi_solver_last_error(self._s).decode())
+        self._check(ierr)
+        return out, Sc
+
+
+def border_product(P, n, m, V, ldv, W, ldw, C_, z, y):
+    """the border product of the bordered operator (hymls_mi_border_product) on device arrays: y[0:n) += V z[n:n+m) and
+    y[n+j] = W(:,j)' z[0:n) + sum_l C[j, l] z[n+l].  V, W (column-major, leading dimensions ldv, ldw), z, y: torch tensors
+    (device memory; host memory with the test-only simulator) or None; C_: (m, m) array-like or None (zero)."""
+    lib = bind_bordered(P._lib)
+    Cm = None if C_ is None else np.asfortranarray(np.asarray(C_, dtype=np.float64))
+    ptr = lambda a: a.data_ptr() if a is not None else None
+    ierr = lib.hymls_mi_border_product(P._h, n, m, ptr(V), ldv, ptr(W), ldw, Cm.ctypes.data if Cm is not None else None,
+                                       ptr(z), ptr(y))
+    if ierr:
+        raise HymlsError(ierr, lib.hymls_mi_last_error(P._h).decode())
 
 
 def orthogonalize(P, n, k, V, ldv, w):

@@ -57,6 +57,28 @@ double hymls_mi_solver_achieved_tol(const hymls_mi_solver_t* s);
  * ended early (below) counts as a restart like one that filled the basis, and "Maximum Restarts" bounds both kinds. */
 int hymls_mi_solver_num_restarts(const hymls_mi_solver_t* s);
 
+#define HYMLS_MI_SOLVER_MAX_BORDER 32
+/* [K V; W' C] [x; s] = [b; t] with the border of the handle (hymls_mi_set_border + Compute) as the border of
+ * the operator AND of the preconditioner (reference HYMLS::BorderedSolver::SetBorder).  One right-hand side.
+ * B, X: n entries, device or host as on_device says.  T, S: host arrays of m doubles (T NULL: zero; S NULL: dropped).
+ * The Krylov vectors are the augmented vectors [x; s] of n + m entries, kept on the device: inner products run over both
+ * parts, and convergence is relative to the first residual of the augmented vector.  Left and right preconditioning,
+ * restarts, the three initial vectors ("Random": border scalar j = hash(seed, global size + j); "Previous" survives while
+ * n + m is unchanged; a "Previous" vector whose true residual is already within tol of the norm of [b; t], as after a
+ * repeated solve of the same system, is returned at once with 0 iterations), both basis storages, num_iters / achieved_tol / num_restarts and the phase timing work as for
+ * hymls_mi_solver_solve; the border product counts as K x (phase 2).
+ * Returns 0, or -1 when the tolerance was not reached (X and S then hold the last iterate).  A handle without a border:
+ * the plain solve of one column, S untouched.  -2: more than HYMLS_MI_SOLVER_MAX_BORDER border columns.  -99: method CG
+ * (the bordered operator [K V; W' C] is indefinite, so CG does not apply: use GMRES), a sharded handle (one GPU only), or a
+ * library built without the border product kernel.  hymls_mi_solver_solve keeps refusing bordered handles with -2. */
+int hymls_mi_solver_solve_bordered(hymls_mi_solver_t* s, const double* B, const double* T, double* X, double* S, int on_device);
+/* building block (as hymls_mi_orthogonalize): y[0:n) += V z[n:n+m),  y[n+j] = W(:,j)' z[0:n) + sum_l C[j + m l] z[n+l].
+ * V, W, z, y device; C host, m x m column-major, may be NULL (zero).  n >= 1, 1 <= m <= HYMLS_MI_SOLVER_MAX_BORDER,
+ * ldv, ldw >= n, z and y distinct arrays of n + m entries; otherwise -2.  Sums in a fixed order without atomics: the
+ * result is bitwise repeatable.  -99 from a library built without the kernel. */
+int hymls_mi_border_product(hymls_mi_t* h, int64_t n, int32_t m, const double* V, int64_t ldv, const double* W, int64_t ldw,
+                            const double* C, const double* z, double* y);
+
 /* Storage of the GMRES basis: 64 (default) keeps FP64 columns, 32 stores them as float (compressed-basis GMRES) and
  * halves the memory and the traffic of the orthogonalisation.  Every other vector, every inner product and the
  * Hessenberg matrix stay FP64: a new column is w / ||w|| formed in FP64 and rounded once.  Takes effect with the next
