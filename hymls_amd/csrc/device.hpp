@@ -144,6 +144,11 @@ inline int spmv_lanes(int32_t nrows, int64_t nnz_hint) {
 }
 void spmv(int32_t nrows, const int32_t* rowptr, const int32_t* col, const double* val,
           const double* x, double* y, double alpha, double beta, int64_t nnz_hint = -1);
+// Y(:, v) = alpha * A X(:, v) + beta * Y(:, v), v < nv (leading dimensions ldx, ldy): the matrix is read once per group of
+// up to four columns, and every column has the bits spmv() gives it (the same lanes per row, the same order).  Host code
+// refers to it only under HYMLS_MI_LOCKSTEP_SOLVER: of the test-only simulators only tests/krylov_lockstep_sim has one.
+void spmv_mv(int32_t nrows, const int32_t* rowptr, const int32_t* col, const double* val, const double* x, int64_t ldx,
+             double* y, int64_t ldy, int nv, double alpha, double beta, int64_t nnz_hint = -1);
 // out[e] = sum_{t in [ptr[e],ptr[e+1])} in[idx[t]]   (deterministic pull-assembly)
 void pull_sum(int64_t n, const int64_t* ptr, const int64_t* idx, const double* in, double* out);
 // Off-diagonal blocks of the level matrix (A12, A21) cut out on the device: for the matrix rows rows[0 .. nrows) keep the

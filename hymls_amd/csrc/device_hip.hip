@@ -416,6 +416,66 @@ void spmv(int32_t nrows, const int32_t* rp, const int32_t* col, const double* va
   launch_check();
 }
 
+// The same product for NV columns X(:, v), Y(:, v) at once: a lane loads each (col, val) pair once and keeps NV sums.  Per
+// column the lanes of a row, the order of its sum and the shuffle reduction are those of k_spmv<L>, so column v has the
+// bits of the single-vector kernel.
+template <int L, int NV>
+__global__ void k_spmv_mv(int32_t nrows, const int32_t* __restrict__ rp, const int32_t* __restrict__ col,
+                          const double* __restrict__ val, const double* __restrict__ x, int64_t ldx, double* __restrict__ y,
+                          int64_t ldy, double alpha, double beta) {
+  const int lane = (int)(threadIdx.x % L);
+  const int rpb = (int)blockDim.x / L;
+  for (int64_t base = (int64_t)blockIdx.x * rpb; base < nrows; base += (int64_t)gridDim.x * rpb) {
+    const int64_t row = base + threadIdx.x / L;
+    double s[NV];
+#pragma unroll
+    for (int v = 0; v < NV; v++) s[v] = 0.0;
+    if (row < nrows) {
+      const int b = rp[row], e = rp[row + 1];
+      for (int k = b + lane; k < e; k += L) {
+        const double a = val[k];
+        const int64_t c = col[k];
+#pragma unroll
+        for (int v = 0; v < NV; v++) s[v] += a * x[c + v * ldx];
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+#pragma unroll
+      for (int off = L / 2; off > 0; off >>= 1) s[v] += __shfl_down(s[v], off, L);
+      if (row < nrows && lane == 0) y[row + v * ldy] = alpha * s[v] + (beta == 0.0 ? 0.0 : beta * y[row + v * ldy]);
+    }
+  }
+}
+template <int L>
+static void spmv_mv_launch(int nv, dim3 grid, int32_t nrows, const int32_t* rp, const int32_t* col, const double* val,
+                           const double* x, int64_t ldx, double* y, int64_t ldy, double alpha, double beta) {
+  switch (nv) {
+    case 2: hipLaunchKernelGGL((k_spmv_mv<L, 2>), grid, dim3(256), 0, g_stream, nrows, rp, col, val, x, ldx, y, ldy, alpha, beta); break;
+    case 3: hipLaunchKernelGGL((k_spmv_mv<L, 3>), grid, dim3(256), 0, g_stream, nrows, rp, col, val, x, ldx, y, ldy, alpha, beta); break;
+    default: hipLaunchKernelGGL((k_spmv_mv<L, 4>), grid, dim3(256), 0, g_stream, nrows, rp, col, val, x, ldx, y, ldy, alpha, beta); break;
+  }
+}
+void spmv_mv(int32_t nrows, const int32_t* rp, const int32_t* col, const double* val, const double* x, int64_t ldx, double* y,
+             int64_t ldy, int nv, double alpha, double beta, int64_t nnz_hint) {
+  if (nrows <= 0) return;
+  for (int v0 = 0; v0 < nv; v0 += 4) {
+    const int g = std::min(4, nv - v0);
+    const double* xg = x + (int64_t)v0 * ldx;
+    double* yg = y + (int64_t)v0 * ldy;
+    if (g == 1) { spmv(nrows, rp, col, val, xg, yg, alpha, beta, nnz_hint); continue; }
+    const int L = spmv_lanes(nrows, nnz_hint);
+    const dim3 grid(nblocks((int64_t)nrows * L, 256));   // the grid of spmv()
+    switch (L) {
+      case 1: spmv_mv_launch<1>(g, grid, nrows, rp, col, val, xg, ldx, yg, ldy, alpha, beta); break;
+      case 2: spmv_mv_launch<2>(g, grid, nrows, rp, col, val, xg, ldx, yg, ldy, alpha, beta); break;
+      case 4: spmv_mv_launch<4>(g, grid, nrows, rp, col, val, xg, ldx, yg, ldy, alpha, beta); break;
+      default: spmv_mv_launch<8>(g, grid, nrows, rp, col, val, xg, ldx, yg, ldy, alpha, beta); break;
+    }
+    launch_check();
+  }
+}
+
 __global__ void k_pull_sum(int64_t n, const int64_t* __restrict__ ptr, const int64_t* __restrict__ idx,
                            const double* __restrict__ in, double* __restrict__ out) {
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {

@@ -20,6 +20,12 @@
 // the two hooks differ: the operator is K x followed by dev::kry_border_product (under HYMLS_MI_BORDERED_SOLVER: the
 // test-only simulators without that launcher leave the macro out and the entry returns -99), the preconditioner is
 // LevelSolver::apply_inverse_bordered with T read from and S written to the tail.  One GPU.
+//
+// Lock-step columns (hymls_mi_solver_set_lockstep, under HYMLS_MI_LOCKSTEP_SOLVER): the columns of a solve call in groups of up
+// to four that advance together.  Every column has a Run and an Arnoldi state of its own and takes its decisions in the same
+// three steps as the single-column solve (Run::cycle_top, record_column, cycle_end); per iteration the active columns share
+// one apply_inverse_mv, one matvec_mv, one batched launch chain of the orthogonalisation (krylov.hpp: KryBatch) and one copy
+// of their coefficients to the host.  One GPU.  Width 1 does not touch any of it.
 #include "../../include/hymls_mi_solver.h"
 #include "capi_internal.hpp"
 #include "krylov.hpp"
@@ -59,6 +65,19 @@ struct hymls_mi_solver {
   bool profiling = false;
   double secs[4] = {0, 0, 0, 0};
   dev::KryTimer* timer = nullptr;
+  // results of every column of the last solve call (hymls_mi_solver_column_result)
+  struct ColResult { int its; double achieved; int restarts; int converged; };
+  std::vector<ColResult> cols;
+  // lock-step columns (hymls_mi_solver_set_lockstep): column 0 of a group works in the buffers above, columns 1..width-1 in
+  // sets of their own, allocated by the first solve that needs them for the n, restart length and basis storage of that solve
+  int lockstep = 1;
+  int lk_width = 0, lk_m = 0, lk_bits = 0;
+  int64_t lk_n = 0;
+  double* lk_V[HYMLS_MI_SOLVER_MAX_LOCKSTEP] = {};      // [1..width): basis
+  double* lk_vec[HYMLS_MI_SOLVER_MAX_LOCKSTEP] = {};    // [1..width): 7 vectors
+  double* lk_work[HYMLS_MI_SOLVER_MAX_LOCKSTEP] = {};   // [1..width): reduction scratch
+  double* lk_out = nullptr;    // [width][KRY_KMAX + 2]: the out areas of all columns in one block, for one copy per step
+  double* lk_stage = nullptr;  // [3][width * ld]: the contiguous operands of the batched ApplyInverse and K x
 };
 
 namespace {
@@ -75,6 +94,8 @@ struct Run {
   int bm = 0;
   const double* dC = nullptr;      // device copy of C
   std::vector<double> bt, bs;      // host T and S of one bordered ApplyInverse
+  dev::KryWork ws{};               // reduction scratch and basis of the column this Run solves (the solver's own, or those of
+  double* Vb = nullptr;            // a lock-step column)
 
   void mark(int phase, bool begin) { if (s->profiling) dev::kry_mark(s->timer, phase, begin); }
   // the two hooks of the iteration; with a border: M^{-1} [in; T] = [out; S] with T and S in the tails, and
@@ -94,7 +115,7 @@ struct Run {
     mark(2, true);
     L->matvec(in, out);
 #ifdef HYMLS_MI_BORDERED_SOLVER
-    if (bm > 0) dev::kry_border_product(nh, bm, L->border_v(), nh, L->border_w(), nh, dC, in, out, s->ws);
+    if (bm > 0) dev::kry_border_product(nh, bm, L->border_v(), nh, L->border_w(), nh, dC, in, out, ws);
 #endif
     mark(2, false);
   }
@@ -106,9 +127,9 @@ struct Run {
     return a[0];
   }
   double dot(const double* a, const double* b) {
-    dev::kry_dot(n, a, b, s->ws);
+    dev::kry_dot(n, a, b, ws);
     double v = 0;
-    dev::d2h(&v, s->ws.out, sizeof v);
+    dev::d2h(&v, ws.out, sizeof v);
     return allsum(v);
   }
   double norm(const double* a) { return std::sqrt(dot(a, a)); }
@@ -116,7 +137,7 @@ struct Run {
   // w <- (I - V V^T)^2 w over the k columns of V, written to dst; hk[0..k) = h1 + h2, hk[k] = ||dst||
   template <class BT>
   void orthogonalize(int k, const BT* Vb, int64_t ldv, double* wv, double* dst, double* hk) {
-    orthogonalize_step(s->ws, comm, dist, n, k, Vb, ldv, wv, dst, hk);
+    orthogonalize_step(ws, comm, dist, n, k, Vb, ldv, wv, dst, hk);
   }
   template <class BT>   // BT: element type of the basis (float only under HYMLS_MI_F32_BASIS)
   static void orthogonalize_step(const dev::KryWork& ws, const Comm* comm, bool dist, int64_t n, int k, const BT* Vb,
@@ -150,79 +171,128 @@ struct Run {
 
   // restarted GMRES (solver.py: Solver._gmres); x holds the start vector.  BT = double: the FP64 basis.  BT = float:
   // the FP32 basis, where the Givens estimate only ends a cycle (at the tolerance, or at KRY_F32_CYCLE_THETA times the
-  // cycle's first residual) and the explicit residual at the top of the next cycle decides; rel is then always explicit
+  // cycle's first residual) and the explicit residual at the top of the next cycle decides; rel is then always explicit.
+  // The host side of one column is the Arnoldi state below and three steps: cycle_top (explicit residual, first column),
+  // record_column (Givens rotations on the coefficients of a new column) and cycle_end (solution update).  gmres() runs
+  // them for one column; the lock-step solve runs the same three for every column of a group, so that a column takes
+  // the same decisions in both
+  struct Arnoldi {
+    int m = 0, its = 0, restarts = 0, cycle = 0, k = 0, k_used = 0;
+    double rel = std::numeric_limits<double>::infinity(), beta = 0.0, beta0 = -1.0;
+    std::vector<double> H, cs, sn, g, hk, y;
+    double& Hk(int i, int j) { return H[(size_t)i + (size_t)(m + 1) * j]; }
+  };
+  void arnoldi_begin(Arnoldi& A) {
+    A = Arnoldi();
+    A.m = std::min(s->p.num_blocks, s->p.max_iters);
+    A.hk.resize(dev::KRY_KMAX + 2);
+  }
+  // top of cycle A.cycle: false when the solve has ended (A.rel is final), else the first basis column is in place
   template <class BT>
-  void gmres(const double* b, int& its, double& rel, int& restarts) {
+  bool cycle_top(const double* b, Arnoldi& A) {
     constexpr bool F32 = sizeof(BT) == 4;
     const hymls_mi_solver_params& P = s->p;
-    const int m = std::min(P.num_blocks, P.max_iters);
     const bool right = P.right != 0;
-    BT* V = (BT*)s->V;
-    its = 0;
-    restarts = 0;
-    rel = std::numeric_limits<double>::infinity();
-    double beta0 = -1.0;
-    std::vector<double> H, cs, sn, g, hk(dev::KRY_KMAX + 2), y;
-    // FP32 basis: the loop is left only at its top, after an explicit residual (one more than the cycles allowed)
-    for (int cycle = 0; cycle <= P.max_restarts + (F32 ? 1 : 0); cycle++) {
-      if (its > 0 || dot(x, x) > 0.0) {
-        matvec(x, t);
-        mark(3, true); dev::kry_sub(n, b, t, r); mark(3, false);
-      } else {
-        dev::d2d(r, b, n * sizeof(double));
-      }
-      double* rr = r;
-      if (!right) { prec(r, w); rr = w; }
-      const double beta = norm(rr);
-      if (beta0 < 0) beta0 = beta;
-      if (beta0 == 0.0) { rel = 0.0; return; }
-      rel = beta / beta0;
-      if (rel <= P.tol || its >= P.max_iters || cycle > P.max_restarts) break;
-      if (cycle > 0) restarts++;
-      mark(3, true); first_column(rr, beta, V); mark(3, false);
-      H.assign((size_t)(m + 1) * m, 0.0);   // H[i + (m + 1) * k]
-      cs.assign(m, 0.0); sn.assign(m, 0.0); g.assign(m + 1, 0.0);
-      g[0] = beta;
-      auto Hk = [&](int i, int k) -> double& { return H[(size_t)i + (size_t)(m + 1) * k]; };
-      int k_used = 0;
-      for (int k = 0; k < m; k++) {
+    // FP32 basis: the loop is left only here, after an explicit residual (one more than the cycles allowed)
+    if (A.cycle > P.max_restarts + (F32 ? 1 : 0)) return false;
+    if (A.its > 0 || dot(x, x) > 0.0) {
+      matvec(x, t);
+      mark(3, true); dev::kry_sub(n, b, t, r); mark(3, false);
+    } else {
+      dev::d2d(r, b, n * sizeof(double));
+    }
+    double* rr = r;
+    if (!right) { prec(r, w); rr = w; }
+    const double beta = norm(rr);
+    A.beta = beta;
+    if (A.beta0 < 0) A.beta0 = beta;
+    if (A.beta0 == 0.0) { A.rel = 0.0; return false; }
+    A.rel = beta / A.beta0;
+    if (A.rel <= P.tol || A.its >= P.max_iters || A.cycle > P.max_restarts) return false;
+    if (A.cycle > 0) A.restarts++;
+    mark(3, true); first_column(rr, beta, (BT*)Vb); mark(3, false);
+    const int m = A.m;
+    A.H.assign((size_t)(m + 1) * m, 0.0);   // H[i + (m + 1) * k]
+    A.cs.assign(m, 0.0); A.sn.assign(m, 0.0); A.g.assign(m + 1, 0.0);
+    A.g[0] = beta;
+    A.k = 0;
+    A.k_used = 0;
+    return true;
+  }
+  // column A.k of the Hessenberg matrix from A.hk[0 .. k + 1]; true when the cycle ends with this column
+  template <class BT>
+  bool record_column(Arnoldi& A) {
+    constexpr bool F32 = sizeof(BT) == 4;
+    const hymls_mi_solver_params& P = s->p;
+    const int k = A.k;
+    std::vector<double>&cs = A.cs, &sn = A.sn, &g = A.g;
+    for (int i = 0; i <= k + 1; i++) A.Hk(i, k) = A.hk[i];
+    for (int i = 0; i < k; i++) {
+      const double tt = cs[i] * A.Hk(i, k) + sn[i] * A.Hk(i + 1, k);
+      A.Hk(i + 1, k) = -sn[i] * A.Hk(i, k) + cs[i] * A.Hk(i + 1, k);
+      A.Hk(i, k) = tt;
+    }
+    const double d = std::hypot(A.Hk(k, k), A.Hk(k + 1, k));
+    cs[k] = A.Hk(k, k) / d; sn[k] = A.Hk(k + 1, k) / d;
+    A.Hk(k, k) = d; A.Hk(k + 1, k) = 0.0;
+    g[k + 1] = -sn[k] * g[k]; g[k] = cs[k] * g[k];
+    A.its++; A.k_used = k + 1;
+    A.rel = std::fabs(g[k + 1]) / A.beta0;
+    if (A.rel <= P.tol || A.its >= P.max_iters) return true;
+    if (F32 && std::fabs(g[k + 1]) <= KRY_F32_CYCLE_THETA * A.beta) return true;
+    A.k = k + 1;
+    return A.k >= A.m;
+  }
+  // the solution update at the end of a cycle; false when the solve has ended
+  template <class BT>
+  bool cycle_end(Arnoldi& A) {
+    constexpr bool F32 = sizeof(BT) == 4;
+    const hymls_mi_solver_params& P = s->p;
+    const bool right = P.right != 0;
+    const int k_used = A.k_used;
+    const BT* V = (const BT*)Vb;
+    // y = H(0:k_used, 0:k_used) \ g, upper triangular
+    std::vector<double>& y = A.y;
+    y.assign(k_used, 0.0);
+    for (int i = k_used - 1; i >= 0; i--) {
+      double v = A.g[i];
+      for (int j = i + 1; j < k_used; j++) v -= A.Hk(i, j) * y[j];
+      y[i] = v / A.Hk(i, i);
+    }
+    dev::h2d(ws.h1, y.data(), k_used * sizeof(double));
+    if (right) {
+      mark(3, true); dev::zero(t, n * sizeof(double)); dev::kry_update(n, k_used, V, ld, ws.h1, t); mark(3, false);
+      prec(t, w);
+      mark(3, true); dev::kry_add(n, w, x); mark(3, false);
+    } else {
+      mark(3, true); dev::kry_update(n, k_used, V, ld, ws.h1, x); mark(3, false);
+    }
+    if (!F32 && (A.rel <= P.tol || A.its >= P.max_iters)) return false;
+    A.cycle++;
+    return true;
+  }
+  template <class BT>
+  void gmres(const double* b, int& its, double& rel, int& restarts) {
+    const bool right = s->p.right != 0;
+    BT* V = (BT*)Vb;
+    Arnoldi A;
+    arnoldi_begin(A);
+    while (cycle_top<BT>(b, A)) {
+      bool ended = false;
+      while (!ended) {
+        const int k = A.k;
         arnoldi_product(V + (int64_t)k * ld, right);
         mark(3, true);
-        new_column(k, V, hk.data());
-        if (!dist) dev::d2h(hk.data(), s->ws.out, (k + 2) * sizeof(double));
+        new_column(k, V, A.hk.data());
+        if (!dist) dev::d2h(A.hk.data(), ws.out, (k + 2) * sizeof(double));
         mark(3, false);
-        for (int i = 0; i <= k + 1; i++) Hk(i, k) = hk[i];
-        for (int i = 0; i < k; i++) {
-          const double tt = cs[i] * Hk(i, k) + sn[i] * Hk(i + 1, k);
-          Hk(i + 1, k) = -sn[i] * Hk(i, k) + cs[i] * Hk(i + 1, k);
-          Hk(i, k) = tt;
-        }
-        const double d = std::hypot(Hk(k, k), Hk(k + 1, k));
-        cs[k] = Hk(k, k) / d; sn[k] = Hk(k + 1, k) / d;
-        Hk(k, k) = d; Hk(k + 1, k) = 0.0;
-        g[k + 1] = -sn[k] * g[k]; g[k] = cs[k] * g[k];
-        its++; k_used = k + 1;
-        rel = std::fabs(g[k + 1]) / beta0;
-        if (rel <= P.tol || its >= P.max_iters) break;
-        if (F32 && std::fabs(g[k + 1]) <= KRY_F32_CYCLE_THETA * beta) break;
+        ended = record_column<BT>(A);
       }
-      // y = H(0:k_used, 0:k_used) \ g, upper triangular
-      y.assign(k_used, 0.0);
-      for (int i = k_used - 1; i >= 0; i--) {
-        double v = g[i];
-        for (int j = i + 1; j < k_used; j++) v -= Hk(i, j) * y[j];
-        y[i] = v / Hk(i, i);
-      }
-      dev::h2d(s->ws.h1, y.data(), k_used * sizeof(double));
-      if (right) {
-        mark(3, true); dev::zero(t, n * sizeof(double)); dev::kry_update(n, k_used, V, ld, s->ws.h1, t); mark(3, false);
-        prec(t, w);
-        mark(3, true); dev::kry_add(n, w, x); mark(3, false);
-      } else {
-        mark(3, true); dev::kry_update(n, k_used, V, ld, s->ws.h1, x); mark(3, false);
-      }
-      if (!F32 && (rel <= P.tol || its >= P.max_iters)) break;
+      if (!cycle_end<BT>(A)) break;
     }
+    its = A.its;
+    rel = A.rel;
+    restarts = A.restarts;
   }
 
   // the pieces of an Arnoldi step that differ between the two basis storages
@@ -234,7 +304,7 @@ struct Run {
   void new_column(int k, double* V, double* hk) {
     double* vn = V + (int64_t)(k + 1) * ld;
     orthogonalize(k + 1, V, ld, w, vn, hk);
-    dev::kry_scale_by(n, vn, s->ws.out + k + 1);   // V[k + 1] = w / ||w|| where ||w|| > 0
+    dev::kry_scale_by(n, vn, ws.out + k + 1);   // V[k + 1] = w / ||w|| where ||w|| > 0
   }
 #ifdef HYMLS_MI_F32_BASIS
   void first_column(const double* rr, double beta, float* V) { dev::kry_round_div(n, rr, beta, V); }
@@ -245,7 +315,7 @@ struct Run {
   }
   void new_column(int k, float* V, double* hk) {
     orthogonalize(k + 1, V, ld, w, w, hk);
-    dev::kry_round_scale_by(n, w, s->ws.out + k + 1, V + (int64_t)(k + 1) * ld);   // (float)(w / ||w||)
+    dev::kry_round_scale_by(n, w, ws.out + k + 1, V + (int64_t)(k + 1) * ld);   // (float)(w / ||w||)
   }
 #endif
 
@@ -271,9 +341,9 @@ struct Run {
       matvec(p, q);
       const double alpha = rz / dot(p, q);
       mark(3, true);
-      dev::kry_cg_xr(n, alpha, p, q, x, r, s->ws);
+      dev::kry_cg_xr(n, alpha, p, q, x, r, ws);
       double rr = 0;
-      dev::d2h(&rr, s->ws.out, sizeof rr);
+      dev::d2h(&rr, ws.out, sizeof rr);
       mark(3, false);
       its++;
       rel = std::sqrt(allsum(rr)) / r0;
@@ -285,6 +355,232 @@ struct Run {
     }
   }
 };
+
+#ifdef HYMLS_MI_LOCKSTEP_SOLVER
+constexpr int LK_MAX = HYMLS_MI_SOLVER_MAX_LOCKSTEP;
+constexpr int64_t LK_OUT = dev::KRY_KMAX + 2;   // doubles of one column's out area
+
+void free_lockstep(hymls_mi_solver* s) {
+  for (int c = 0; c < LK_MAX; c++) {
+    dev::free(s->lk_V[c]); dev::free(s->lk_vec[c]); dev::free(s->lk_work[c]);
+    s->lk_V[c] = s->lk_vec[c] = s->lk_work[c] = nullptr;
+  }
+  dev::free(s->lk_out); dev::free(s->lk_stage);
+  s->lk_out = s->lk_stage = nullptr;
+  s->lk_width = 0; s->lk_m = 0; s->lk_bits = 0; s->lk_n = 0;
+}
+
+// the buffers of columns 1..width-1 next to the solver's own (sized like them), the block of out areas and the staging
+// columns.  A failed allocation frees what this attempt took and throws -3: the solver's own buffers are untouched
+void ensure_lockstep(hymls_mi_solver* s, int width, bool gm) {
+  const bool fits = s->lk_width >= width && s->lk_n == s->n && (!gm || (s->lk_m >= s->m_alloc && s->lk_bits == s->bits_alloc));
+  if (fits) return;
+  dev::sync();
+  free_lockstep(s);
+  const size_t basis = gm ? (size_t)(s->m_alloc + 1) * s->ld * (s->bits_alloc / 8) : 0;
+  const size_t vecs = (size_t)7 * s->ld * sizeof(double), work = dev::kry_work_doubles() * sizeof(double);
+  const size_t outs = (size_t)width * LK_OUT * sizeof(double), stage = (size_t)3 * width * s->ld * sizeof(double);
+  const size_t total = (size_t)(width - 1) * (basis + vecs + work) + outs + stage;
+  try {
+    for (int c = 1; c < width; c++) {
+      if (basis) s->lk_V[c] = (double*)dev::alloc(basis);
+      s->lk_vec[c] = (double*)dev::alloc(vecs);
+      s->lk_work[c] = (double*)dev::alloc(work);
+    }
+    s->lk_out = (double*)dev::alloc(outs);
+    s->lk_stage = (double*)dev::alloc(stage);
+  } catch (...) {
+    free_lockstep(s);
+    char buf[192];
+    std::snprintf(buf, sizeof buf, "lock-step solve: could not allocate %zu bytes of device memory for %d columns (the solver "
+                  "still works at width 1)", total, width);
+    throw hymls::Error(-3, buf);
+  }
+  s->lk_width = width; s->lk_n = s->n; s->lk_m = gm ? s->m_alloc : 0; s->lk_bits = gm ? s->bits_alloc : 0;
+}
+
+// A group of nc <= width consecutive columns that advance together, one Krylov iteration per step.  Every column has a Run
+// of its own (vectors, basis, reduction scratch) and takes its decisions in the steps of Run that the single-column solve
+// takes them in; what happens once per cycle (explicit residual, first column, solution update) runs through the
+// single-column launchers, column by column.  Per iteration the active columns share one ApplyInverse, one K x, one launch
+// chain of the orthogonalisation and one copy of their coefficients to the host; a column that has ended leaves the batch.
+struct Lockstep {
+  hymls_mi_solver* s;
+  LevelSolver* L;
+  int64_t n, ld;
+  int nc = 0;
+  Run R[LK_MAX];
+  Run::Arnoldi A[LK_MAX];
+  const double* b[LK_MAX];
+  bool active[LK_MAX];
+  int its[LK_MAX];
+  double rel[LK_MAX];
+  std::vector<double> host;   // the out areas of the group on the host
+
+  double* stage(int which, int j) const { return s->lk_stage + ((size_t)which * s->lk_width + j) * ld; }
+  void mark(int phase, bool begin) { R[0].mark(phase, begin); }
+  void prec_mv(int which_in, int which_out, int na) {
+    mark(1, true);
+    L->apply_inverse_mv(stage(which_in, 0), ld, stage(which_out, 0), ld, na);
+    mark(1, false);
+  }
+  void matvec_mv(int which_in, int which_out, int na) {
+    mark(2, true);
+    L->matvec_mv(stage(which_in, 0), ld, stage(which_out, 0), ld, na);
+    mark(2, false);
+  }
+  // the out areas of columns act[0] .. act[na - 1] (first `count` doubles each) in one copy
+  void fetch(const int* act, int na, int64_t count) {
+    const int first = act[0], last = act[na - 1];
+    dev::d2h(host.data() + first * LK_OUT, s->lk_out + first * LK_OUT, ((size_t)(last - first) * LK_OUT + count) * sizeof(double));
+  }
+
+  template <class BT>
+  void gmres() {
+    constexpr bool F32 = sizeof(BT) == 4;
+    const bool right = s->p.right != 0;
+    host.assign((size_t)LK_MAX * LK_OUT, 0.0);
+    for (int c = 0; c < nc; c++) {
+      R[c].arnoldi_begin(A[c]);
+      active[c] = R[c].template cycle_top<BT>(b[c], A[c]);
+    }
+    for (;;) {
+      int act[LK_MAX], na = 0;
+      for (int c = 0; c < nc; c++) if (active[c]) act[na++] = c;
+      if (na == 0) break;
+      // the current basis column of every active column, side by side (FP32 basis: widened on the way)
+      mark(3, true);
+      dev::KryVecBatch vb{};
+      vb.nb = na;
+      for (int j = 0; j < na; j++) {
+        const int c = act[j];
+        const BT* vk = (const BT*)R[c].Vb + (int64_t)A[c].k * ld;
+        if (F32) { vb.a[j] = vk; vb.y[j] = stage(0, j); }
+        else dev::d2d(stage(0, j), vk, n * sizeof(double));
+      }
+      if (F32) dev::kry_widen_mv(n, vb);
+      mark(3, false);
+      if (right) { prec_mv(0, 1, na); matvec_mv(1, 2, na); }
+      else { matvec_mv(0, 1, na); prec_mv(1, 2, na); }
+      // ICGS(2) of column j of the product against the basis of its own column, and the new basis column
+      mark(3, true);
+      dev::KryBatch B;
+      B.nb = na;
+      dev::KryVecBatch sb{};
+      sb.nb = na;
+      int kmax = 0;
+      for (int j = 0; j < na; j++) {
+        const int c = act[j], kk = A[c].k + 1;
+        BT* vn = (BT*)R[c].Vb + (int64_t)kk * ld;
+        B.k[j] = kk;
+        B.V[j] = R[c].Vb;
+        B.w[j] = stage(2, j);
+        B.dst[j] = F32 ? stage(2, j) : (double*)vn;
+        B.ws[j] = R[c].ws;
+        sb.a[j] = stage(2, j);
+        sb.y[j] = vn;
+        sb.d[j] = R[c].ws.out + kk;
+        if (c == act[na - 1]) kmax = kk;
+      }
+      dev::kry_pass_a_mv(n, ld, B, F32);
+      dev::kry_pass_b_mv(n, ld, B, F32);
+      dev::kry_pass_c_mv(n, ld, B, F32);
+      if (F32) dev::kry_round_scale_by_mv(n, sb);   // (float)(w / ||w||)
+      else dev::kry_scale_by_mv(n, sb);             // V[k + 1] = w / ||w|| where ||w|| > 0
+      fetch(act, na, kmax + 1);
+      mark(3, false);
+      for (int j = 0; j < na; j++) {
+        const int c = act[j];
+        std::copy(host.begin() + c * LK_OUT, host.begin() + c * LK_OUT + A[c].k + 2, A[c].hk.begin());
+        if (!R[c].template record_column<BT>(A[c])) continue;
+        active[c] = R[c].template cycle_end<BT>(A[c]) && R[c].template cycle_top<BT>(b[c], A[c]);
+      }
+    }
+    for (int c = 0; c < nc; c++) { its[c] = A[c].its; rel[c] = A[c].rel; }
+  }
+
+  // preconditioned CG: the start of Run::cg column by column, then its loop with the active columns side by side
+  void cg() {
+    const hymls_mi_solver_params& P = s->p;
+    host.assign((size_t)LK_MAX * LK_OUT, 0.0);
+    double rz[LK_MAX], r0[LK_MAX];
+    for (int c = 0; c < nc; c++) {
+      Run& r = R[c];
+      if (r.dot(r.x, r.x) > 0.0) {
+        r.matvec(r.x, r.t);
+        mark(3, true); dev::kry_sub(n, b[c], r.t, r.r); mark(3, false);
+      } else {
+        dev::d2d(r.r, b[c], n * sizeof(double));
+      }
+      r.prec(r.r, r.w);
+      dev::d2d(r.p, r.w, n * sizeof(double));
+      rz[c] = r.dot(r.r, r.w);
+      r0[c] = r.norm(r.r);
+      its[c] = 0;
+      rel[c] = 1.0;
+      active[c] = true;
+      if (r0[c] == 0.0) { rel[c] = 0.0; active[c] = false; }
+      else if (!(its[c] < P.max_iters)) active[c] = false;
+    }
+    for (;;) {
+      int act[LK_MAX], na = 0;
+      for (int c = 0; c < nc; c++) if (active[c]) act[na++] = c;
+      if (na == 0) break;
+      dev::KryVecBatch vb{};
+      vb.nb = na;
+      for (int j = 0; j < na; j++) {
+        const int c = act[j];
+        dev::d2d(stage(0, j), R[c].p, n * sizeof(double));
+        vb.a[j] = R[c].p; vb.b[j] = stage(2, j);            // p . q with q = K p
+        vb.part[j] = R[c].ws.part; vb.out[j] = R[c].ws.out;
+      }
+      matvec_mv(0, 2, na);
+      dev::kry_dot_mv(n, vb);
+      fetch(act, na, 1);
+      mark(3, true);
+      for (int j = 0; j < na; j++) {
+        const int c = act[j];
+        vb.s[j] = rz[c] / host[c * LK_OUT];                // alpha
+        vb.y[j] = R[c].x; vb.r[j] = R[c].r;
+      }
+      dev::kry_cg_xr_mv(n, vb);
+      fetch(act, na, 1);
+      mark(3, false);
+      int cont[LK_MAX], ncont = 0;
+      for (int j = 0; j < na; j++) {
+        const int c = act[j];
+        its[c]++;
+        rel[c] = std::sqrt(host[c * LK_OUT]) / r0[c];
+        if (rel[c] <= P.tol) active[c] = false;
+        else cont[ncont++] = c;
+      }
+      if (ncont == 0) continue;
+      dev::KryVecBatch zb{};
+      zb.nb = ncont;
+      for (int j = 0; j < ncont; j++) {
+        const int c = cont[j];
+        dev::d2d(stage(0, j), R[c].r, n * sizeof(double));
+        zb.a[j] = R[c].r; zb.b[j] = stage(1, j);            // r . z with z = M^{-1} r
+        zb.part[j] = R[c].ws.part; zb.out[j] = R[c].ws.out;
+      }
+      prec_mv(0, 1, ncont);
+      dev::kry_dot_mv(n, zb);
+      fetch(cont, ncont, 1);
+      mark(3, true);
+      for (int j = 0; j < ncont; j++) {
+        const int c = cont[j];
+        const double rz_new = host[c * LK_OUT];
+        zb.s[j] = rz_new / rz[c];
+        zb.a[j] = stage(1, j); zb.y[j] = R[c].p;            // p <- z + beta p
+        rz[c] = rz_new;
+        active[c] = its[c] < P.max_iters;
+      }
+      dev::kry_cg_p_mv(n, zb);
+      mark(3, false);
+    }
+  }
+};
+#endif
 
 uint64_t splitmix64(uint64_t z) {
   z += 0x9E3779B97F4A7C15ull;
@@ -302,6 +598,9 @@ void check_params(const hymls_mi_solver_params& p) {
 }
 
 void free_buffers(hymls_mi_solver* s) {
+#ifdef HYMLS_MI_LOCKSTEP_SOLVER
+  free_lockstep(s);
+#endif
   dev::free(s->V); dev::free(s->vec); dev::free(s->work); dev::free(s->bc);
   s->V = s->vec = s->work = s->bc = nullptr;
   s->n = s->ld = 0; s->m_alloc = 0; s->have_prev = false;
@@ -406,6 +705,9 @@ int solve_columns(hymls_mi_solver* s, const HandleView& hv_, int bm, const doubl
     R.bt.assign(bm, 0.0);
     R.bs.assign(bm, 0.0);
   }
+  R.ws = s->ws;
+  R.Vb = s->V;
+  s->cols.clear();
   double* v = s->vec;
   R.x = v; R.r = v + s->ld; R.w = v + 2 * s->ld; R.t = v + 3 * s->ld; R.p = v + 4 * s->ld;
   R.prev = v + 5 * s->ld; R.bst = v + 6 * s->ld;
@@ -419,6 +721,58 @@ int solve_columns(hymls_mi_solver* s, const HandleView& hv_, int bm, const doubl
       rnd[i] = (double)(u >> 11) * (1.0 / 9007199254740992.0) * 2.0 - 1.0;
     }
   }
+#ifdef HYMLS_MI_LOCKSTEP_SOLVER
+  // lock-step columns: groups of `width` consecutive columns (the bordered solve has one right-hand side and ignores it)
+  const int width = bm == 0 ? std::min(s->lockstep, std::max(nvec, 1)) : 1;
+  if (width > 1) {
+    ensure_lockstep(s, width, gm);
+    Lockstep G{s, L, n, s->ld};
+    for (int c0 = 0; c0 < nvec; c0 += width) {
+      G.nc = std::min(width, nvec - c0);
+      for (int c = 0; c < G.nc; c++) {
+        Run& Rc = G.R[c];
+        Rc = R;
+        double* vc = c == 0 ? s->vec : s->lk_vec[c];
+        Rc.x = vc; Rc.r = vc + s->ld; Rc.w = vc + 2 * s->ld; Rc.t = vc + 3 * s->ld; Rc.p = vc + 4 * s->ld;
+        Rc.prev = vc + 5 * s->ld; Rc.bst = vc + 6 * s->ld;
+        if (c > 0) {
+          Rc.Vb = s->lk_V[c];
+          Rc.ws.part = s->lk_work[c];
+          Rc.ws.h1 = Rc.ws.part + (size_t)dev::KRY_MAXGRID * dev::KRY_KMAX;
+          Rc.ws.h2 = Rc.ws.h1 + dev::KRY_KMAX;
+        }
+        Rc.ws.out = s->lk_out + c * LK_OUT;   // the out areas of a group: one block, one copy per step
+        const double* b = B + (int64_t)(c0 + c) * ldb;
+        if (!on_device) { dev::h2d(Rc.bst, b, n * sizeof(double)); b = Rc.bst; }
+        G.b[c] = b;
+        // "Previous": every column of the group starts from the solution stored before the group
+        if (s->p.initial_vector == 1) dev::h2d(Rc.x, rnd.data(), n * sizeof(double));
+        else if (s->p.initial_vector == 2 && s->have_prev) dev::d2d(Rc.x, R.prev, n * sizeof(double));
+        else dev::zero(Rc.x, n * sizeof(double));
+      }
+      R.mark(0, true);
+      if (!gm) G.cg();
+#ifdef HYMLS_MI_F32_BASIS
+      else if (s->basis_bits == 32) G.gmres<float>();
+#endif
+      else G.gmres<double>();
+      R.mark(0, false);
+      for (int c = 0; c < G.nc; c++) {
+        const int restarts = gm ? G.A[c].restarts : 0;
+        s->its = G.its[c];
+        s->restarts = restarts;
+        s->achieved = G.rel[c];
+        s->cols.push_back({G.its[c], G.rel[c], restarts, G.rel[c] <= s->p.tol ? 1 : 0});
+        if (on_device) dev::d2d(X + (int64_t)(c0 + c) * ldx, G.R[c].x, n * sizeof(double));
+        else dev::d2h(X + (int64_t)(c0 + c) * ldx, G.R[c].x, n * sizeof(double));
+        if (!(G.rel[c] <= s->p.tol)) status = -1;
+      }
+      dev::d2d(R.prev, G.R[G.nc - 1].x, n * sizeof(double));   // the group's last column
+      s->have_prev = true;
+    }
+    nvec = 0;   // nothing is left for the column-by-column loop
+  }
+#endif
   for (int c = 0; c < nvec; c++) {
     const double* b = B + (int64_t)c * ldb;
     if (bm > 0) {                // the augmented right-hand side [b; t] is always staged
@@ -455,6 +809,7 @@ int solve_columns(hymls_mi_solver* s, const HandleView& hv_, int bm, const doubl
     s->its = its;
     s->restarts = restarts;
     s->achieved = rel;
+    s->cols.push_back({its, rel, restarts, rel <= s->p.tol ? 1 : 0});
     dev::d2d(R.prev, R.x, n * sizeof(double));
     s->have_prev = true;
     if (on_device) dev::d2d(X + (int64_t)c * ldx, R.x, nh * sizeof(double));
@@ -485,6 +840,10 @@ int hymls_mi_solver_solve(hymls_mi_solver_t* s, const double* B, int64_t ldb, do
   check_params(s->p);
   const int64_t n = hv_.top->num_owned();
   HYMLS_CHECK(nvec <= 1 || (ldb >= n && ldx >= n), -2, "solve: leading dimension smaller than the number of rows");
+  HYMLS_CHECK(s->lockstep == 1 || !hv_.comm->distributed(), -99, "solve with lock-step columns: one GPU only (sharded handles are not supported)");
+#ifndef HYMLS_MI_LOCKSTEP_SOLVER
+  HYMLS_CHECK(s->lockstep == 1, -99, "this build has no batched Krylov launchers (a test-only simulator without them)");
+#endif
   status = solve_columns(s, hv_, 0, B, ldb, nullptr, X, ldx, nullptr, nvec, on_device);
   SOLVER_END
   return status;
@@ -638,6 +997,155 @@ int hymls_mi_border_product(hymls_mi_t* h, int64_t n, int32_t m, const double* V
       dev::sync();
     } catch (...) { dev::free(work); throw; }
     dev::free(work);
+#endif
+  } catch (const hymls::Error& e) { *hv.err = e.what(); return e.code; }
+  catch (const std::exception& e) { *hv.err = e.what(); return -3; }
+  return 0;
+}
+
+int hymls_mi_solver_set_lockstep(hymls_mi_solver_t* s, int width) {
+  if (!s) return -2;
+  SOLVER_BEGIN
+  HYMLS_CHECK(width >= 1 && width <= HYMLS_MI_SOLVER_MAX_LOCKSTEP, -2, "lock-step columns: 1 to 4");
+#ifndef HYMLS_MI_LOCKSTEP_SOLVER
+  HYMLS_CHECK(width == 1, -99, "this build has no batched Krylov launchers (a test-only simulator without them)");
+#else
+  if (width != s->lockstep && s->lk_width > 0) {   // another width: the next solve allocates what it needs
+    dev::sync();
+    free_lockstep(s);
+  }
+#endif
+  s->lockstep = width;
+  SOLVER_END
+  return 0;
+}
+int hymls_mi_solver_lockstep(const hymls_mi_solver_t* s) { return s ? s->lockstep : 0; }
+
+int hymls_mi_solver_column_result(const hymls_mi_solver_t* s, int v, int* iters, double* achieved_tol, int* restarts, int* converged) {
+  if (!s || v < 0 || v >= (int)s->cols.size()) return -2;
+  const hymls_mi_solver::ColResult& c = s->cols[v];
+  if (iters) *iters = c.its;
+  if (achieved_tol) *achieved_tol = c.achieved;
+  if (restarts) *restarts = c.restarts;
+  if (converged) *converged = c.converged;
+  return 0;
+}
+
+int hymls_mi_matvec_mv(hymls_mi_t* h, const double* X, int64_t ldx, double* Y, int64_t ldy, int nvec, int on_device) {
+  if (!h) return -2;
+  HandleView hv = handle_view(h);
+  try {
+#ifndef HYMLS_MI_LOCKSTEP_SOLVER
+    (void)X; (void)ldx; (void)Y; (void)ldy; (void)nvec; (void)on_device;
+    throw hymls::Error(-99, "this build has no multi-vector K x kernel (a test-only simulator without it)");
+#else
+    dev::bind(hv.ctx);
+    HYMLS_CHECK(hv.computed && hv.top, -1, "matvec_mv needs a computed preconditioner (device copy of K)");
+    HYMLS_CHECK(!hv.comm->distributed(), -99, "matvec_mv: one GPU only (sharded handles are not supported)");
+    const int64_t n = hv.top->num_owned();
+    HYMLS_CHECK(nvec >= 0 && (nvec == 0 || (X && Y && ldx >= n && ldy >= n)), -2, "matvec_mv: need non-null X, Y and ldx, ldy >= n");
+    if (nvec == 0) return 0;
+    if (on_device) {
+      hv.top->matvec_mv(X, ldx, Y, ldy, nvec);
+      dev::sync();
+    } else {
+      double* buf = (double*)dev::alloc((size_t)2 * nvec * n * sizeof(double));
+      try {
+        for (int v = 0; v < nvec; v++) dev::h2d(buf + (int64_t)v * n, X + (int64_t)v * ldx, n * sizeof(double));
+        hv.top->matvec_mv(buf, n, buf + (int64_t)nvec * n, n, nvec);
+        for (int v = 0; v < nvec; v++) dev::d2h(Y + (int64_t)v * ldy, buf + (int64_t)(nvec + v) * n, n * sizeof(double));
+      } catch (...) { dev::free(buf); throw; }
+      dev::free(buf);
+    }
+#endif
+  } catch (const hymls::Error& e) { *hv.err = e.what(); return e.code; }
+  catch (const std::exception& e) { *hv.err = e.what(); return -3; }
+  return 0;
+}
+
+}  // extern "C"
+
+#ifdef HYMLS_MI_LOCKSTEP_SOLVER
+namespace {
+// nb independent ICGS(2) steps in one launch chain (the orthogonalisation of one lock-step iteration); vnext: FP32 basis only
+template <class BT>
+void orthogonalize_mv(const HandleView& hv, int64_t n, int32_t nb, const int32_t* k, const BT* V, int64_t ldv, int64_t vstride,
+                      double* W, int64_t ldw, float* vnext, int64_t ldn, double* hcoef, int64_t ldh, double* wnorm) {
+  constexpr bool F32 = sizeof(BT) == 4;
+  dev::bind(hv.ctx);
+  HYMLS_CHECK(!hv.comm->distributed(), -99, "orthogonalize_mv: one GPU only (sharded handles are not supported)");
+  HYMLS_CHECK(nb >= 1 && nb <= HYMLS_MI_SOLVER_MAX_LOCKSTEP && k && n >= 1 && ldv >= n && ldw >= n && V && W && hcoef && wnorm &&
+              (!vnext || ldn >= n), -2, "orthogonalize_mv: need 1 <= nb <= 4, n >= 1, ldv, ldw >= n and non-null arrays");
+  int kmax = 0;
+  for (int v = 0; v < nb; v++) {
+    HYMLS_CHECK(k[v] >= 1 && k[v] <= dev::KRY_KMAX, -2, "orthogonalize_mv: need 1 <= k[v] <= 256");
+    kmax = std::max(kmax, (int)k[v]);
+  }
+  HYMLS_CHECK(ldh >= kmax, -2, "orthogonalize_mv: ldh smaller than the largest k");
+  const size_t per = dev::kry_work_doubles();
+  double* work = (double*)dev::alloc((size_t)nb * per * sizeof(double));
+  dev::KryBatch B;
+  dev::KryVecBatch sb{};
+  B.nb = sb.nb = nb;
+  for (int v = 0; v < nb; v++) {
+    dev::KryWork& ws = B.ws[v];
+    ws.part = work + (size_t)v * per;
+    ws.h1 = ws.part + (size_t)dev::KRY_MAXGRID * dev::KRY_KMAX;
+    ws.h2 = ws.h1 + dev::KRY_KMAX;
+    ws.out = ws.h2 + dev::KRY_KMAX;
+    B.k[v] = k[v];
+    B.V[v] = V + (int64_t)v * vstride;
+    B.w[v] = B.dst[v] = W + (int64_t)v * ldw;
+    sb.a[v] = B.w[v];
+    sb.y[v] = vnext ? vnext + (int64_t)v * ldn : nullptr;
+    sb.d[v] = ws.out + k[v];
+  }
+  std::vector<double> hk(dev::KRY_KMAX + 1);
+  try {
+    dev::kry_pass_a_mv(n, ldv, B, F32);
+    dev::kry_pass_b_mv(n, ldv, B, F32);
+    dev::kry_pass_c_mv(n, ldv, B, F32);
+    if (F32 && vnext) dev::kry_round_scale_by_mv(n, sb);
+    for (int v = 0; v < nb; v++) {
+      dev::d2h(hk.data(), B.ws[v].out, (k[v] + 1) * sizeof(double));
+      std::copy(hk.begin(), hk.begin() + k[v], hcoef + (int64_t)v * ldh);
+      wnorm[v] = hk[k[v]];
+    }
+  } catch (...) { dev::free(work); throw; }
+  dev::free(work);
+}
+}  // namespace
+#endif
+
+extern "C" {
+
+int hymls_mi_orthogonalize_mv(hymls_mi_t* h, int64_t n, int32_t nb, const int32_t* k, const double* V, int64_t ldv,
+                              int64_t vstride, double* W, int64_t ldw, double* hcoef, int64_t ldh, double* wnorm) {
+  if (!h) return -2;
+  HandleView hv = handle_view(h);
+  try {
+#ifndef HYMLS_MI_LOCKSTEP_SOLVER
+    (void)n; (void)nb; (void)k; (void)V; (void)ldv; (void)vstride; (void)W; (void)ldw; (void)hcoef; (void)ldh; (void)wnorm;
+    throw hymls::Error(-99, "this build has no batched Krylov launchers (a test-only simulator without them)");
+#else
+    orthogonalize_mv<double>(hv, n, nb, k, V, ldv, vstride, W, ldw, nullptr, 0, hcoef, ldh, wnorm);
+#endif
+  } catch (const hymls::Error& e) { *hv.err = e.what(); return e.code; }
+  catch (const std::exception& e) { *hv.err = e.what(); return -3; }
+  return 0;
+}
+
+int hymls_mi_orthogonalize_mv_f32(hymls_mi_t* h, int64_t n, int32_t nb, const int32_t* k, const float* V, int64_t ldv,
+                                  int64_t vstride, double* W, int64_t ldw, float* vnext, int64_t ldn, double* hcoef, int64_t ldh,
+                                  double* wnorm) {
+  if (!h) return -2;
+  HandleView hv = handle_view(h);
+  try {
+#if !defined(HYMLS_MI_LOCKSTEP_SOLVER) || !defined(HYMLS_MI_F32_BASIS)
+    (void)n; (void)nb; (void)k; (void)V; (void)ldv; (void)vstride; (void)W; (void)ldw; (void)vnext; (void)ldn; (void)hcoef; (void)ldh; (void)wnorm;
+    throw hymls::Error(-99, "this build has no batched FP32 basis launchers (a test-only simulator without them)");
+#else
+    orthogonalize_mv<float>(hv, n, nb, k, V, ldv, vstride, W, ldw, vnext, ldn, hcoef, ldh, wnorm);
 #endif
   } catch (const hymls::Error& e) { *hv.err = e.what(); return e.code; }
   catch (const std::exception& e) { *hv.err = e.what(); return -3; }

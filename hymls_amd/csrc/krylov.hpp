@@ -101,6 +101,44 @@ constexpr int KRY_BORDER_CHUNK = 8;
 void kry_border_product(int64_t n, int32_t m, const double* V, int64_t ldv, const double* W, int64_t ldw, const double* dC,
                         const double* z, double* y, const KryWork& ws);
 
+// ---- lock-step columns ("MI Lockstep Columns", hymls_mi_solver_set_lockstep): up to KRY_LOCKSTEP_MAX independent
+// columns per launch, the column is blockIdx.y.  Every launcher below gives column v bit for bit what its single-column
+// launcher above gives with the operands of column v: the slice of column v strides by ITS OWN grid (kry_tile_grid(n, k[v]),
+// kry_row_grid(n), vec_grid(n)) and writes that many partials, whatever the other columns of the launch need; the launch
+// itself has the largest grid and the largest LDS size of the batch, and the workgroups of a column beyond its own grid
+// leave before their first barrier.  The operand table is a kernel argument (it lives in the kernarg segment, which the
+// device reads): no copy per step, and k may change from step to step.  Implemented by krylov_hip.hip and by the
+// test-only tests/krylov_lockstep_sim; krylov.cpp refers to them only under HYMLS_MI_LOCKSTEP_SOLVER.
+constexpr int KRY_LOCKSTEP_MAX = 4;
+struct KryBatch {                      // the columns of one batched orthogonalisation launch
+  int32_t nb = 0;                      // columns, 1..KRY_LOCKSTEP_MAX
+  int32_t k[KRY_LOCKSTEP_MAX];         // basis columns of column v, 1..KRY_KMAX
+  const void* V[KRY_LOCKSTEP_MAX];     // its basis (double or float, as the launcher says), leading dimension ldv
+  double* w[KRY_LOCKSTEP_MAX];         // the vector that is orthogonalised (passes A, B in place)
+  double* dst[KRY_LOCKSTEP_MAX];       // pass C: dst <- w - V h2 (may be w)
+  KryWork ws[KRY_LOCKSTEP_MAX];        // its reduction scratch, laid out as for the single-column launchers
+};
+void kry_pass_a_mv(int64_t n, int64_t ldv, const KryBatch& b, bool f32);
+void kry_pass_b_mv(int64_t n, int64_t ldv, const KryBatch& b, bool f32);
+void kry_pass_c_mv(int64_t n, int64_t ldv, const KryBatch& b, bool f32);
+struct KryVecBatch {                   // the columns of one batched vector pass
+  int32_t nb = 0;
+  const void* a[KRY_LOCKSTEP_MAX];     // first input
+  const double* b[KRY_LOCKSTEP_MAX];   // second input
+  void* y[KRY_LOCKSTEP_MAX];           // output (updated in place where the single-column pass does so)
+  double* r[KRY_LOCKSTEP_MAX];         // second output (kry_cg_xr_mv)
+  const double* d[KRY_LOCKSTEP_MAX];   // device scalar
+  double s[KRY_LOCKSTEP_MAX];          // host scalar
+  double* part[KRY_LOCKSTEP_MAX];      // stage-one partials of a reduction
+  double* out[KRY_LOCKSTEP_MAX];       // its result
+};
+void kry_scale_by_mv(int64_t n, const KryVecBatch& b);         // y <- y / *d where *d > 0                    (kry_scale_by)
+void kry_round_scale_by_mv(int64_t n, const KryVecBatch& b);   // (float*) y <- (float)(a / *d), or (float) a (kry_round_scale_by)
+void kry_widen_mv(int64_t n, const KryVecBatch& b);            // (double*) y <- (double)(const float*) a     (kry_widen)
+void kry_dot_mv(int64_t n, const KryVecBatch& b);              // out[0] = a . b                              (kry_dot)
+void kry_cg_xr_mv(int64_t n, const KryVecBatch& b);            // y += s a, r -= s b, out[0] = r . r          (kry_cg_xr: p = a, q = b, x = y)
+void kry_cg_p_mv(int64_t n, const KryVecBatch& b);             // y <- a + s y                                (kry_cg_p: z = a, p = y)
+
 // phase timing of a solve: events recorded on the stream (the simulator takes host clock readings)
 struct KryTimer;
 KryTimer* kry_timer_create();

@@ -268,6 +268,194 @@ __global__ void __launch_bounds__(256) k_kry_border_tail(const double* __restric
   }
 }
 
+// ---- lock-step columns (krylov.hpp: KryBatch, KryVecBatch): blockIdx.y is the column.  Each kernel is the body of its
+// single-column kernel above with gridDim.x replaced by the column's own grid `own`: a column strides by the grid its
+// single-column launch would have had and writes that many partials, so its sums are added in the same order and give the
+// same bits whatever the other columns of the launch are.  Workgroups past `own` leave before the first barrier.
+template <bool UPD, class BT>
+__global__ void __launch_bounds__(256) k_kry_tile_mv(int64_t n, int64_t ldv, KryBatch B, int4 owns) {
+  extern __shared__ double sm[];
+  constexpr bool F32 = sizeof(BT) == 4;
+  constexpr int T = KRY_TILE, LT = F32 ? KRY_LD_TILE_F32 : KRY_LD_TILE;
+  const int c = blockIdx.y;
+  const int k = B.k[c];
+  const int64_t ntiles = (n + T - 1) / T;
+  const int own = c == 0 ? owns.x : (c == 1 ? owns.y : (c == 2 ? owns.z : owns.w));   // kry_tile_grid[_f32](n, k) of this column
+  if ((int)blockIdx.x >= own) return;
+  const BT* __restrict__ V = (const BT*)B.V[c];
+  double* w = B.w[c];
+  const double* __restrict__ h1 = B.ws[c].h1;
+  double* __restrict__ part = B.ws[c].part;
+  BT* Vs = F32 ? (BT*)(sm + T + KRY_KMAX + 4 * T) : (BT*)sm;
+  double* ws = F32 ? sm : sm + (size_t)LT * k;
+  double* hs = ws + T;
+  double* red = hs + KRY_KMAX;
+  const int t = threadIdx.x;
+  if (UPD)
+    for (int j = t; j < k; j += 256) hs[j] = h1[j];
+  double acc = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += own) {
+    const int64_t r0 = tile * T;
+    const int rows = (int)(n - r0 < T ? n - r0 : T);
+    __syncthreads();
+    for (int e = t; e < T * k; e += 256) {
+      const int r = e & (T - 1), j = e / T;
+      Vs[j * LT + r] = r < rows ? V[(int64_t)j * ldv + r0 + r] : (BT)0;
+    }
+    if (t < T) ws[t] = t < rows ? w[r0 + t] : 0.0;
+    __syncthreads();
+    if (UPD) {
+      const int r = t & (T - 1), q = t / T;
+      double s = 0.0;
+      for (int j = q; j < k; j += 4) s += (double)Vs[j * LT + r] * hs[j];
+      red[q * T + r] = s;
+      __syncthreads();
+      if (t < T) {
+        const double v = ws[t] - (((red[t] + red[T + t]) + red[2 * T + t]) + red[3 * T + t]);
+        ws[t] = v;
+        if (t < rows) w[r0 + t] = v;
+      }
+      __syncthreads();
+    }
+    if (t < k) {
+      const BT* cc = Vs + t * LT;
+#pragma unroll 8
+      for (int r = 0; r < T; r++) acc += (double)cc[r] * ws[r];
+    }
+  }
+  if (t < k) part[(int64_t)blockIdx.x * k + t] = acc;
+}
+
+// pass C of the batch: own grid kry_row_grid(n), the same for every column, is the launch grid
+template <class BT>
+__global__ void __launch_bounds__(256) k_kry_rows_mv(int64_t n, int64_t ldv, KryBatch B) {
+  __shared__ double hs[KRY_KMAX];
+  __shared__ double red[256];
+  const int c = blockIdx.y;
+  const int k = B.k[c];
+  const BT* __restrict__ V = (const BT*)B.V[c];
+  const double* __restrict__ h = B.ws[c].h2;
+  const double* w = B.w[c];
+  double* dst = B.dst[c];
+  const int t = threadIdx.x;
+  for (int j = t; j < k; j += 256) hs[j] = h[j];
+  __syncthreads();
+  double ss = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + t; i < n; i += (int64_t)gridDim.x * 256) {
+    const BT* v = V + i;
+    double s = 0.0;
+#pragma unroll 8
+    for (int j = 0; j < k; j++) s += (double)v[(int64_t)j * ldv] * hs[j];
+    const double x = w[i] - s;
+    dst[i] = x;
+    ss += x * x;
+  }
+  red[t] = ss;
+  block_sum256(red);
+  if (t == 0) B.ws[c].part[blockIdx.x] = red[0];
+}
+
+// stage two of passes A (UPD false: h1) and B (h2, out = h1 + h2): grid (largest k, columns); nbs[c]: the partials of column c
+template <bool UPD>
+__global__ void __launch_bounds__(256) k_kry_reduce_mv(KryBatch B, int4 nbs) {
+  __shared__ double red[256];
+  const int c = blockIdx.y, j = blockIdx.x, t = threadIdx.x;
+  const int k = B.k[c];
+  if (j >= k) return;
+  const int nb = c == 0 ? nbs.x : (c == 1 ? nbs.y : (c == 2 ? nbs.z : nbs.w));
+  const double* __restrict__ part = B.ws[c].part;
+  double s = 0.0;
+  for (int b = t; b < nb; b += 256) s += part[(int64_t)b * k + j];
+  red[t] = s;
+  block_sum256(red);
+  if (t == 0) {
+    if (UPD) { B.ws[c].h2[j] = red[0]; B.ws[c].out[j] = B.ws[c].h1[j] + red[0]; }
+    else B.ws[c].h1[j] = red[0];
+  }
+}
+__global__ void __launch_bounds__(256) k_kry_reduce_norm_mv(KryBatch B, int nb) {
+  __shared__ double red[256];
+  const int c = blockIdx.y, t = threadIdx.x;
+  const double* __restrict__ part = B.ws[c].part;
+  double* dst = B.ws[c].out + B.k[c];
+  double s = 0.0;
+  for (int b = t; b < nb; b += 256) s += part[b];
+  red[t] = s;
+  block_sum256(red);
+  if (t == 0) { dst[0] = std::sqrt(red[0]); dst[1] = red[0]; }
+}
+// stage two of the batched dots: out[c][0] = the sum of the nb partials of column c (k_kry_reduce with k = 1)
+__global__ void __launch_bounds__(256) k_kry_reduce1_mv(KryVecBatch B, int nb) {
+  __shared__ double red[256];
+  const int c = blockIdx.y, t = threadIdx.x;
+  const double* __restrict__ part = B.part[c];
+  double s = 0.0;
+  for (int b = t; b < nb; b += 256) s += part[b];
+  red[t] = s;
+  block_sum256(red);
+  if (t == 0) B.out[c][0] = red[0];
+}
+
+__global__ void __launch_bounds__(256) k_kry_scale_by_mv(int64_t n, KryVecBatch B) {
+  const int c = blockIdx.y;
+  double* x = (double*)B.y[c];
+  const double s = *B.d[c];
+  if (!(s > 0.0)) return;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) x[i] = x[i] / s;
+}
+__global__ void __launch_bounds__(256) k_kry_widen_mv(int64_t n, KryVecBatch B) {
+  const int c = blockIdx.y;
+  const float* __restrict__ v = (const float*)B.a[c];
+  double* __restrict__ t = (double*)B.y[c];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) t[i] = (double)v[i];
+}
+__global__ void __launch_bounds__(256) k_kry_round_scale_by_mv(int64_t n, KryVecBatch B) {
+  const int c = blockIdx.y;
+  const double* __restrict__ x = (const double*)B.a[c];
+  float* __restrict__ y = (float*)B.y[c];
+  const double s = *B.d[c];
+  const bool pos = s > 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    y[i] = (float)(pos ? x[i] / s : x[i]);
+}
+__global__ void __launch_bounds__(256) k_kry_dot_mv(int64_t n, KryVecBatch B) {
+  __shared__ double red[256];
+  const int c = blockIdx.y;
+  const double* __restrict__ x = (const double*)B.a[c];
+  const double* __restrict__ y = B.b[c];
+  double s = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) s += x[i] * y[i];
+  red[threadIdx.x] = s;
+  block_sum256(red);
+  if (threadIdx.x == 0) B.part[c][blockIdx.x] = red[0];
+}
+__global__ void __launch_bounds__(256) k_kry_cg_xr_mv(int64_t n, KryVecBatch B) {
+  __shared__ double red[256];
+  const int c = blockIdx.y;
+  const double alpha = B.s[c];
+  const double* __restrict__ p = (const double*)B.a[c];
+  const double* __restrict__ q = B.b[c];
+  double* __restrict__ x = (double*)B.y[c];
+  double* __restrict__ r = B.r[c];
+  double s = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    x[i] = x[i] + alpha * p[i];
+    const double v = r[i] - alpha * q[i];
+    r[i] = v;
+    s += v * v;
+  }
+  red[threadIdx.x] = s;
+  block_sum256(red);
+  if (threadIdx.x == 0) B.part[c][blockIdx.x] = red[0];
+}
+__global__ void __launch_bounds__(256) k_kry_cg_p_mv(int64_t n, KryVecBatch B) {
+  const int c = blockIdx.y;
+  const double beta = B.s[c];
+  const double* __restrict__ z = (const double*)B.a[c];
+  double* __restrict__ p = (double*)B.y[c];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = z[i] + beta * p[i];
+}
+
 static inline void kcheck() { KRY_CHECK(hipGetLastError()); }
 
 template <bool UPD, class BT>
@@ -402,6 +590,95 @@ void kry_border_product(int64_t n, int32_t m, const double* V, int64_t ldv, cons
     }
   }
   hipLaunchKernelGGL(k_kry_border_tail, dim3(1), dim3(256), 0, kstream(), ws.part, nb, n, m, dC, z, y);
+  kcheck();
+}
+
+// ---- lock-step launchers
+static void check_batch(const KryBatch& b) {
+  if (b.nb < 1 || b.nb > KRY_LOCKSTEP_MAX) throw Error(-2, "batched orthogonalisation: 1 <= columns <= 4");
+  for (int c = 0; c < b.nb; c++)
+    if (b.k[c] < 1 || b.k[c] > KRY_KMAX) throw Error(-2, "orthogonalisation: 1 <= k <= 256 columns");
+}
+template <bool UPD, class BT>
+static void tile_pass_mv(int64_t n, int64_t ldv, const KryBatch& b) {
+  check_batch(b);
+  constexpr bool F32 = sizeof(BT) == 4;
+  int own[KRY_LOCKSTEP_MAX] = {0, 0, 0, 0};
+  int grid = 1, kmax = 1;
+  size_t shm = 0;
+  for (int c = 0; c < b.nb; c++) {
+    own[c] = F32 ? kry_tile_grid_f32(n, b.k[c]) : kry_tile_grid(n, b.k[c]);
+    grid = std::max(grid, own[c]);
+    kmax = std::max(kmax, (int)b.k[c]);
+    shm = std::max(shm, F32 ? kry_tile_lds_f32(b.k[c]) : kry_tile_lds(b.k[c]));
+  }
+  static thread_local int attr_device = -1;   // per device and per basis type, as in tile_pass
+  int devno = 0;
+  KRY_CHECK(hipGetDevice(&devno));
+  if (attr_device != devno) {
+    const int most = (int)(F32 ? kry_tile_lds_f32(KRY_KMAX) : kry_tile_lds(KRY_KMAX));
+    KRY_CHECK(hipFuncSetAttribute((const void*)k_kry_tile_mv<false, BT>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+    KRY_CHECK(hipFuncSetAttribute((const void*)k_kry_tile_mv<true, BT>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+    attr_device = devno;
+  }
+  const int4 owns = make_int4(own[0], own[1], own[2], own[3]);
+  hipLaunchKernelGGL((k_kry_tile_mv<UPD, BT>), dim3(grid, b.nb), dim3(256), shm, kstream(), n, ldv, b, owns);
+  kcheck();
+  hipLaunchKernelGGL(k_kry_reduce_mv<UPD>, dim3(kmax, b.nb), dim3(256), 0, kstream(), b, owns);
+  kcheck();
+}
+void kry_pass_a_mv(int64_t n, int64_t ldv, const KryBatch& b, bool f32) {
+  if (f32) tile_pass_mv<false, float>(n, ldv, b); else tile_pass_mv<false, double>(n, ldv, b);
+}
+void kry_pass_b_mv(int64_t n, int64_t ldv, const KryBatch& b, bool f32) {
+  if (f32) tile_pass_mv<true, float>(n, ldv, b); else tile_pass_mv<true, double>(n, ldv, b);
+}
+void kry_pass_c_mv(int64_t n, int64_t ldv, const KryBatch& b, bool f32) {
+  check_batch(b);
+  const int nb = kry_row_grid(n);
+  if (f32) hipLaunchKernelGGL(k_kry_rows_mv<float>, dim3(nb, b.nb), dim3(256), 0, kstream(), n, ldv, b);
+  else hipLaunchKernelGGL(k_kry_rows_mv<double>, dim3(nb, b.nb), dim3(256), 0, kstream(), n, ldv, b);
+  kcheck();
+  hipLaunchKernelGGL(k_kry_reduce_norm_mv, dim3(1, b.nb), dim3(256), 0, kstream(), b, nb);
+  kcheck();
+}
+static void check_vec_batch(const KryVecBatch& b) {
+  if (b.nb < 1 || b.nb > KRY_LOCKSTEP_MAX) throw Error(-2, "batched vector pass: 1 <= columns <= 4");
+}
+void kry_scale_by_mv(int64_t n, const KryVecBatch& b) {
+  check_vec_batch(b);
+  hipLaunchKernelGGL(k_kry_scale_by_mv, dim3(vec_grid(n), b.nb), dim3(256), 0, kstream(), n, b);
+  kcheck();
+}
+void kry_round_scale_by_mv(int64_t n, const KryVecBatch& b) {
+  check_vec_batch(b);
+  hipLaunchKernelGGL(k_kry_round_scale_by_mv, dim3(vec_grid(n), b.nb), dim3(256), 0, kstream(), n, b);
+  kcheck();
+}
+void kry_widen_mv(int64_t n, const KryVecBatch& b) {
+  check_vec_batch(b);
+  hipLaunchKernelGGL(k_kry_widen_mv, dim3(vec_grid(n), b.nb), dim3(256), 0, kstream(), n, b);
+  kcheck();
+}
+void kry_dot_mv(int64_t n, const KryVecBatch& b) {
+  check_vec_batch(b);
+  const int nb = vec_grid(n);
+  hipLaunchKernelGGL(k_kry_dot_mv, dim3(nb, b.nb), dim3(256), 0, kstream(), n, b);
+  kcheck();
+  hipLaunchKernelGGL(k_kry_reduce1_mv, dim3(1, b.nb), dim3(256), 0, kstream(), b, nb);
+  kcheck();
+}
+void kry_cg_xr_mv(int64_t n, const KryVecBatch& b) {
+  check_vec_batch(b);
+  const int nb = vec_grid(n);
+  hipLaunchKernelGGL(k_kry_cg_xr_mv, dim3(nb, b.nb), dim3(256), 0, kstream(), n, b);
+  kcheck();
+  hipLaunchKernelGGL(k_kry_reduce1_mv, dim3(1, b.nb), dim3(256), 0, kstream(), b, nb);
+  kcheck();
+}
+void kry_cg_p_mv(int64_t n, const KryVecBatch& b) {
+  check_vec_batch(b);
+  hipLaunchKernelGGL(k_kry_cg_p_mv, dim3(vec_grid(n), b.nb), dim3(256), 0, kstream(), n, b);
   kcheck();
 }
 

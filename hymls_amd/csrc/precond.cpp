@@ -2821,6 +2821,14 @@ void LevelSolver::matvec(const double* x, double* y) {
   dev::spmv(nown, d_mv_row_, d_mv_col_, d_mv_val_, d_mv_x_, y, 1.0, 0.0);
 }
 
+#ifdef HYMLS_MI_LOCKSTEP_SOLVER
+void LevelSolver::matvec_mv(const double* x, int64_t ldx, double* y, int64_t ldy, int nv) {
+  dev::Range range("MatrixBlock", level_ + 1, "Apply");
+  HYMLS_CHECK(!comm_->distributed(), -99, "matvec_mv: one GPU only (sharded handles are not supported)");
+  dev::spmv_mv(K_.n, d_krow_, d_kcol_, d_kval_, x, ldx, y, ldy, nv, 1.0, 0.0);
+}
+#endif
+
 void LevelSolver::add_stats(ApplyStats& st, bool as_coarse) const {
   double f = 0, fs = 0, sp = 0, sep = 0, vec = 0;
   for (size_t c = 0; c < cls_.size(); c++) {

@@ -257,6 +257,11 @@ class LevelSolver : public Operator {
   // y = K x on the rows this rank owns (vectors in the layout of apply_inverse); sharded: collective, the values
   // of the columns owned elsewhere are imported first (the Epetra_CrsMatrix::Apply of the reference's Krylov loop)
   void matvec(const double* x, double* y);
+#ifdef HYMLS_MI_LOCKSTEP_SOLVER
+  // Y(:, v) = K X(:, v), v < nv, with K read once per group of up to four columns (dev::spmv_mv); every column has the
+  // bits of matvec.  One GPU only: a sharded handle throws -99
+  void matvec_mv(const double* x, int64_t ldx, double* y, int64_t ldy, int nv);
+#endif
 
   // introspection
   const HierMap& hiermap() const { return hm_; }

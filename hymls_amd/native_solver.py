@@ -56,6 +56,33 @@ _SIG_BORDERED = {
 }
 
 
+# bound apart from _SIG as well (bind_lockstep): lock-step columns and their building blocks
+_SIG_LOCKSTEP = {
+    "hymls_mi_solver_set_lockstep": (C.c_int, [C.c_void_p, C.c_int]),
+    "hymls_mi_solver_lockstep": (C.c_int, [C.c_void_p]),
+    "hymls_mi_solver_column_result": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                                C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hymls_mi_matvec_mv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int]),
+    "hymls_mi_orthogonalize_mv": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "hymls_mi_orthogonalize_mv_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                                C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                C.c_void_p]),
+}
+MAX_LOCKSTEP = 4
+
+
+def bind_lockstep(lib):
+    """declare the lock-step symbols on a loaded library (once); AttributeError if it lacks one"""
+    if not getattr(lib, "_hymls_lockstep_bound", False):
+        for name, (res, args) in _SIG_LOCKSTEP.items():
+            f = getattr(lib, name)
+            f.restype = res
+            f.argtypes = args
+        lib._hymls_lockstep_bound = True
+    return lib
+
+
 def bind_bordered(lib):
     """declare the two bordered symbols on a loaded library (once); AttributeError if it lacks one"""
     if not getattr(lib, "_hymls_bordered_bound", False):
@@ -109,6 +136,15 @@ def basis_bits(params):
     return BASIS_STORAGE[storage]
 
 
+def lockstep_columns(params):
+    """"MI Lockstep Columns" of the Solver sublist (1, the default, to 4): the columns of a multi-column solve that advance
+    together (hymls_mi_solver_set_lockstep)"""
+    width = int(params.get("Solver", params).get("MI Lockstep Columns", 1))
+    if not 1 <= width <= MAX_LOCKSTEP:
+        raise ValueError("MI Lockstep Columns must lie in 1..%d" % MAX_LOCKSTEP)
+    return width
+
+
 class NativeSolver:
     """K x = b with the library's own Krylov loop; P: a computed hymls_amd.Preconditioner (sharded or not)."""
 
@@ -118,9 +154,12 @@ class NativeSolver:
         self._s = C.c_void_p()
         self._params = solver_params(params or {})
         bits = basis_bits(params or {})
+        width = lockstep_columns(params or {})
         ierr = self._lib.hymls_mi_solver_create(C.byref(self._s), P._h, C.byref(self._params))
         if not ierr:
             ierr = self._lib.hymls_mi_solver_set_basis_storage(self._s, bits)
+        if not ierr and width != 1:
+            ierr = bind_lockstep(self._lib).hymls_mi_solver_set_lockstep(self._s, width)
         if ierr:
             msg = self._lib.hymls_mi_solver_last_error(self._s).decode() if self._s else "create failed"
             self.close()
@@ -138,6 +177,9 @@ class NativeSolver:
         self._check(self._lib.hymls_mi_solver_set_params(self._s, C.byref(p)))
         self._params = p
         self._check(self._lib.hymls_mi_solver_set_basis_storage(self._s, bits))
+        width = lockstep_columns(params)
+        if width != 1 or getattr(self._lib, "_hymls_lockstep_bound", False):
+            self._check(bind_lockstep(self._lib).hymls_mi_solver_set_lockstep(self._s, width))
 
     def SetTolerance(self, tol):
         self._check(self._lib.hymls_mi_solver_set_tolerance(self._s, float(tol)))
@@ -155,6 +197,19 @@ class NativeSolver:
 
     def getBasisStorage(self):
         return {v: k for k, v in BASIS_STORAGE.items()}[self._lib.hymls_mi_solver_basis_storage(self._s)]
+
+    def getLockstep(self):
+        """the columns of a multi-column solve that advance together ("MI Lockstep Columns")"""
+        return bind_lockstep(self._lib).hymls_mi_solver_lockstep(self._s)
+
+    def getColumnResults(self):
+        """one dict per column of the last ApplyInverse: iterations, achieved_tol, restarts, converged"""
+        lib = bind_lockstep(self._lib)
+        out = []
+        its, tol, rst, conv = C.c_int(), C.c_double(), C.c_int(), C.c_int()
+        while lib.hymls_mi_solver_column_result(self._s, len(out), C.byref(its), C.byref(tol), C.byref(rst), C.byref(conv)) == 0:
+            out.append({"iterations": its.value, "achieved_tol": tol.value, "restarts": rst.value, "converged": bool(conv.value)})
+        return out
 
     def ApplyInverse(self, B, X=None):
         """solve K X = B.  B: torch tensor on the device (n,) or (nvec, n) (float64, contiguous), or a numpy array (n,)
@@ -265,6 +320,51 @@ def border_product(P, n, m, V, ldv, W, ldw, C_, z, y):
                                        ptr(z), ptr(y))
     if ierr:
         raise HymlsError(ierr, lib.hymls_mi_last_error(P._h).decode())
+
+
+def matvec_mv(P, X, ldx, Y, ldy, nvec):
+    """Y(:, v) = K X(:, v), v < nvec (hymls_mi_matvec_mv): K is read once per group of up to four columns.  X, Y: torch
+    tensors (device memory; host memory with the test-only simulator) or numpy arrays in host memory, column-major with
+    leading dimensions ldx, ldy."""
+    lib = bind_lockstep(P._lib)
+    on_device = hasattr(X, "data_ptr")
+    ptr = (lambda a: a.data_ptr()) if on_device else (lambda a: a.ctypes.data)
+    ierr = lib.hymls_mi_matvec_mv(P._h, ptr(X), ldx, ptr(Y), ldy, nvec, int(on_device))
+    if ierr:
+        raise HymlsError(ierr, lib.hymls_mi_last_error(P._h).decode())
+    return Y
+
+
+def _orthogonalize_mv(P, f32, n, ks, V, ldv, vstride, W, ldw, vnext, ldn):
+    lib = bind_lockstep(P._lib)
+    nb = len(ks)
+    kk = np.ascontiguousarray(ks, dtype=np.int32)
+    ldh = max(int(kk.max()), 1) if nb else 1
+    h = np.zeros((max(nb, 1), ldh))
+    nrm = np.zeros(max(nb, 1))
+    ptr = lambda a: a.data_ptr() if a is not None else None
+    if f32:
+        ierr = lib.hymls_mi_orthogonalize_mv_f32(P._h, n, nb, kk.ctypes.data, ptr(V), ldv, vstride, ptr(W), ldw, ptr(vnext), ldn,
+                                                 h.ctypes.data, ldh, nrm.ctypes.data)
+    else:
+        ierr = lib.hymls_mi_orthogonalize_mv(P._h, n, nb, kk.ctypes.data, ptr(V), ldv, vstride, ptr(W), ldw, h.ctypes.data, ldh,
+                                             nrm.ctypes.data)
+    if ierr:
+        raise HymlsError(ierr, lib.hymls_mi_last_error(P._h).decode())
+    return [h[v, :kk[v]].copy() for v in range(nb)], nrm[:nb]
+
+
+def orthogonalize_mv(P, n, ks, V, ldv, vstride, W, ldw):
+    """len(ks) independent ICGS(2) steps in one launch chain (hymls_mi_orthogonalize_mv): column v of W (leading dimension
+    ldw) is orthogonalised in place against the ks[v] columns of its own basis V[v * vstride:] (leading dimension ldv).
+    Returns ([h1 + h2 of column v], norms); each column has the bits of ``orthogonalize``."""
+    return _orthogonalize_mv(P, False, n, ks, V, ldv, vstride, W, ldw, None, 0)
+
+
+def orthogonalize_mv_f32(P, n, ks, V, ldv, vstride, W, ldw, vnext=None, ldn=0):
+    """the same against float bases (hymls_mi_orthogonalize_mv_f32); vnext (optional float32 tensor, leading dimension ldn)
+    receives float32(W(:, v) / ||W(:, v)||)."""
+    return _orthogonalize_mv(P, True, n, ks, V, ldv, vstride, W, ldw, vnext, ldn)
 
 
 def orthogonalize(P, n, k, V, ldv, w):

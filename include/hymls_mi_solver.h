@@ -45,7 +45,8 @@ int hymls_mi_solver_create(hymls_mi_solver_t** s, hymls_mi_t* h, const hymls_mi_
 int hymls_mi_solver_set_params(hymls_mi_solver_t* s, const hymls_mi_solver_params* p);
 int hymls_mi_solver_set_tolerance(hymls_mi_solver_t* s, double tol);
 
-/* Solves K X(:, v) = B(:, v) for v = 0..nvec-1, one column after the other (block size 1).  B, X: column-major with
+/* Solves K X(:, v) = B(:, v) for v = 0..nvec-1, one column after the other (block size 1), or in lock-step groups
+ * (hymls_mi_solver_set_lockstep below).  B, X: column-major with
  * leading dimensions ldb, ldx (>= this rank's row count); device pointers if on_device, else host memory.
  * "Previous" starts each column from the solution of the column (or call) solved before it.
  * Returns 0 when every column converged, -1 when one did not (X then holds the last iterate), < -1 on errors.
@@ -91,6 +92,30 @@ int hymls_mi_border_product(hymls_mi_t* h, int64_t n, int32_t m, const double* V
 int hymls_mi_solver_set_basis_storage(hymls_mi_solver_t* s, int bits);
 int hymls_mi_solver_basis_storage(const hymls_mi_solver_t* s);
 
+/* Lock-step columns: hymls_mi_solver_solve with width L > 1 takes the nvec columns in groups of L consecutive columns (the
+ * last group may be smaller), and the columns of a group advance together, one Krylov iteration per step.  Each column does
+ * exactly the arithmetic of its own single-column solve; per step the group shares one ApplyInverse and one K x on its
+ * columns side by side (the factors and K are read once for the group), one launch chain of the orthogonalisation whose
+ * per-column slices repeat the single-column decomposition, and one copy of the coefficients to the host.  A column that
+ * converges, has a zero first residual, or runs out of iterations or restarts leaves the group, and the others go on with
+ * a smaller batch; with the FP32 basis the columns may sit at different positions of their cycles.  For the initial
+ * vectors "Zero" and "Random", X, the per-column results and the return status are bitwise those of width 1 (the
+ * default).  The one difference: with "Previous" every column of a group starts from the solution stored before the
+ * group (the last column of the preceding group or call), and the group's last column is stored afterwards.
+ * GMRES and CG.  Every column beyond the first has its own basis, seven work vectors and reduction scratch, allocated by
+ * the first solve that needs them; a failed allocation returns -3 with the bytes asked for in the message, frees what the
+ * attempt took and leaves the solver usable at width 1.  width outside 1..HYMLS_MI_SOLVER_MAX_LOCKSTEP: -2.  One GPU: a
+ * solve with width > 1 on a sharded handle returns -99.  hymls_mi_solver_solve_bordered ignores the width.  A library
+ * built without the batched launchers (a test-only simulator) returns -99 for width > 1. */
+#define HYMLS_MI_SOLVER_MAX_LOCKSTEP 4
+int hymls_mi_solver_set_lockstep(hymls_mi_solver_t* s, int width);
+int hymls_mi_solver_lockstep(const hymls_mi_solver_t* s);
+/* results of column v of the last hymls_mi_solver_solve call (every width; a bordered solve has one column): 0, or -2 for
+ * v out of range.  Any of the four pointers may be null.  num_iters / achieved_tol / num_restarts keep describing the
+ * last column. */
+int hymls_mi_solver_column_result(const hymls_mi_solver_t* s, int v, int* iters, double* achieved_tol, int* restarts,
+                                  int* converged);
+
 /* phase timing with events on the stream (adds a synchronisation at the end of every solve while on).
  * which: 0 whole solve, 1 ApplyInverse, 2 K x, 3 orthogonalisation + updates; seconds summed since profiling was
  * switched on. */
@@ -111,6 +136,24 @@ int hymls_mi_orthogonalize(hymls_mi_t* h, int64_t n, int32_t k, const double* V,
  * Returns -99 from a library built without the FP32 basis kernels. */
 int hymls_mi_orthogonalize_f32(hymls_mi_t* h, int64_t n, int32_t k, const float* V, int64_t ldv, double* w, float* vnext,
                                double* hcoef, double* wnorm);
+
+/* Building blocks of the lock-step solve.  One GPU: sharded handles return -99 from all three, and so does a library built
+ * without the batched launchers.
+ * Y(:, v) = K X(:, v), v < nvec (column-major, ldx, ldy >= the row count; device pointers if on_device): K is read once per
+ * group of up to four columns, and every column is bitwise equal to hymls_mi_matvec. */
+int hymls_mi_matvec_mv(hymls_mi_t* h, const double* X, int64_t ldx, double* Y, int64_t ldy, int nvec, int on_device);
+/* nb independent ICGS(2) steps in one launch chain: column v orthogonalises W(:, v) (device, ldw >= n) in place against the
+ * k[v] columns of its own basis V + v * vstride (device, leading dimension ldv >= n); hcoef (host) receives k[v] values
+ * h1 + h2 at hcoef + v * ldh (ldh >= the largest k), wnorm[v] (host) the norm.  Each column is bitwise equal to
+ * hymls_mi_orthogonalize with k[v].  1 <= nb <= HYMLS_MI_SOLVER_MAX_LOCKSTEP, 1 <= k[v] <= HYMLS_MI_SOLVER_MAX_BLOCKS (k: host);
+ * otherwise -2. */
+int hymls_mi_orthogonalize_mv(hymls_mi_t* h, int64_t n, int32_t nb, const int32_t* k, const double* V, int64_t ldv,
+                              int64_t vstride, double* W, int64_t ldw, double* hcoef, int64_t ldh, double* wnorm);
+/* the same against float bases (vstride in floats); vnext (device, may be null) receives (float)(W(:, v) / ||W(:, v)||) at
+ * vnext + v * ldn (ldn >= n floats), as in hymls_mi_orthogonalize_f32 */
+int hymls_mi_orthogonalize_mv_f32(hymls_mi_t* h, int64_t n, int32_t nb, const int32_t* k, const float* V, int64_t ldv,
+                                  int64_t vstride, double* W, int64_t ldw, float* vnext, int64_t ldn, double* hcoef,
+                                  int64_t ldh, double* wnorm);
 
 const char* hymls_mi_solver_last_error(const hymls_mi_solver_t* s);
 void hymls_mi_solver_destroy(hymls_mi_solver_t* s);
