@@ -26,6 +26,14 @@
 // three steps as the single-column solve (Run::cycle_top, record_column, cycle_end); per iteration the active columns share
 // one apply_inverse_mv, one matvec_mv, one batched launch chain of the orthogonalisation (krylov.hpp: KryBatch) and one copy
 // of their coefficients to the host.  One GPU.  Width 1 does not touch any of it.
+//
+// Projection vectors (hymls_mi_solver_set_projection, under HYMLS_MI_PROJECTED_SOLVER; the reference's
+// BaseSolver::setProjectionVectors with HYMLS::ProjectedOperator): the solve runs in the complement of a small space.  Only
+// the two hooks and the start vector change: the operator is (I - BV V') K (I - V BV'), the preconditioner
+// M^{-1} (I - BV H^{-1} BV' M^{-1}) with H = BV' M^{-1} BV, and the start vector is projected.  Every projector is one
+// dev::kry_oblique_project (krylov.hpp).  The preconditioner has two forms that are equal in exact arithmetic: the literal
+// one applies M^{-1} twice as the reference does, the folded one applies it once and subtracts Z (H^{-1} (BV' M^{-1} x))
+// with Z = M^{-1} BV formed once per Compute.  One GPU, one column at a time.
 #include "../../include/hymls_mi_solver.h"
 #include "capi_internal.hpp"
 #include "krylov.hpp"
@@ -78,6 +86,15 @@ struct hymls_mi_solver {
   double* lk_work[HYMLS_MI_SOLVER_MAX_LOCKSTEP] = {};   // [1..width): reduction scratch
   double* lk_out = nullptr;    // [width][KRY_KMAX + 2]: the out areas of all columns in one block, for one copy per step
   double* lk_stage = nullptr;  // [3][width * ld]: the contiguous operands of the batched ApplyInverse and K x
+  // projection vectors (hymls_mi_solver_set_projection): one device block, allocated when they are set
+  int pm = 0;                      // columns (0: no projection)
+  int p_form = 0;                  // preconditioner: 0 folded, 1 literal
+  bool p_same = true;              // BV = V: one copy
+  int64_t p_n = 0, p_ld = 0;       // rows and leading dimension of V, BV and Z
+  double* p_buf = nullptr;         // V, BV (unless BV = V), Z, one work vector, G = H^{-1}, reduction scratch
+  double *pV = nullptr, *pBV = nullptr, *pZ = nullptr, *p_tmp = nullptr, *pG = nullptr;
+  dev::KryWork pws{};              // part[kry_row_grid(n) * m], h1[m]
+  int p_compute = -1;              // hymls_mi_num_compute of the handle when Z and H were formed (-1: not yet)
 };
 
 namespace {
@@ -96,6 +113,13 @@ struct Run {
   std::vector<double> bt, bs;      // host T and S of one bordered ApplyInverse
   dev::KryWork ws{};               // reduction scratch and basis of the column this Run solves (the solver's own, or those of
   double* Vb = nullptr;            // a lock-step column)
+  // projection vectors (pm > 0): the solver's device copies, its work vector and the scratch of the projectors
+  int pm = 0;
+  bool literal = false;
+  int64_t pld = 0;
+  const double *pV = nullptr, *pBV = nullptr, *pZ = nullptr, *pG = nullptr;
+  double* ptmp = nullptr;
+  dev::KryWork pws{};
 
   void mark(int phase, bool begin) { if (s->profiling) dev::kry_mark(s->timer, phase, begin); }
   // the two hooks of the iteration; with a border: M^{-1} [in; T] = [out; S] with T and S in the tails, and
@@ -104,6 +128,17 @@ struct Run {
     mark(1, true);
     if (bm == 0) {
       L->apply_inverse_mv(in, n, out, n, 1);
+#ifdef HYMLS_MI_PROJECTED_SOLVER
+      // M^{-1} (I - BV H^{-1} BV' M^{-1}) in: with d = H^{-1} (BV' out), literally M^{-1} (in - BV d) as the reference
+      // applies it, or folded out - Z d with Z = M^{-1} BV
+      if (pm > 0 && literal) {
+        dev::kry_proj_coeffs(n, pm, pBV, pld, pG, out, pws);
+        dev::kry_proj_update(n, pm, pBV, pld, in, ptmp, pws);
+        L->apply_inverse_mv(ptmp, n, out, n, 1);
+      } else if (pm > 0) {
+        dev::kry_oblique_project(n, pm, pBV, pld, pG, pZ, pld, out, out, pws);
+      }
+#endif
     } else {
       dev::d2h(bt.data(), in + nh, bm * sizeof(double));
       L->apply_inverse_bordered(in, bt.data(), out, bs.data());
@@ -113,6 +148,13 @@ struct Run {
   }
   void matvec(const double* in, double* out) {
     mark(2, true);
+#ifdef HYMLS_MI_PROJECTED_SOLVER
+    if (pm > 0) {                  // (I - BV V') K (I - V BV') in
+      dev::kry_oblique_project(n, pm, pBV, pld, nullptr, pV, pld, in, ptmp, pws);
+      L->matvec(ptmp, out);
+      dev::kry_oblique_project(n, pm, pV, pld, nullptr, pBV, pld, out, out, pws);
+    } else
+#endif
     L->matvec(in, out);
 #ifdef HYMLS_MI_BORDERED_SOLVER
     if (bm > 0) dev::kry_border_product(nh, bm, L->border_v(), nh, L->border_w(), nh, dC, in, out, ws);
@@ -597,6 +639,77 @@ void check_params(const hymls_mi_solver_params& p) {
               "Num Blocks must lie in 1..256");
 }
 
+void free_projection(hymls_mi_solver* s) {
+  dev::free(s->p_buf);
+  s->p_buf = s->pV = s->pBV = s->pZ = s->p_tmp = s->pG = nullptr;
+  s->pws = dev::KryWork{};
+  s->pm = 0; s->p_n = s->p_ld = 0; s->p_same = true; s->p_compute = -1;
+}
+
+#ifdef HYMLS_MI_PROJECTED_SOLVER
+// hands the projection of the solver to a Run
+void bind_projection(const hymls_mi_solver* s, Run& R) {
+  R.pm = s->pm; R.literal = s->p_form == 1; R.pld = s->p_ld;
+  R.pV = s->pV; R.pBV = s->pBV; R.pZ = s->pZ; R.pG = s->pG; R.ptmp = s->p_tmp; R.pws = s->pws;
+}
+
+// Z = M^{-1} BV in groups of up to four columns, H = BV' Z column by column with the dots kernel, and G = H^{-1} from an LU
+// factorisation with partial pivoting on the host (H G = I); formed again when the handle has been computed anew
+void form_projection(hymls_mi_solver* s, LevelSolver* L) {
+  const int m = s->pm;
+  const int64_t n = s->p_n, ld = s->p_ld;
+  for (int c = 0; c < m; c += 4) L->apply_inverse_mv(s->pBV + c * ld, ld, s->pZ + c * ld, ld, std::min(4, m - c));
+  std::vector<double> H((size_t)m * m), G((size_t)m * m, 0.0);
+  for (int k = 0; k < m; k++) {
+    dev::kry_proj_coeffs(n, m, s->pBV, ld, nullptr, s->pZ + k * ld, s->pws);
+    dev::d2h(H.data() + (size_t)k * m, s->pws.h1, m * sizeof(double));
+  }
+  for (int j = 0; j < m; j++) G[j + (size_t)m * j] = 1.0;
+  for (int k = 0; k < m; k++) {
+    int piv = k;
+    for (int i = k + 1; i < m; i++)
+      if (std::fabs(H[i + (size_t)m * k]) > std::fabs(H[piv + (size_t)m * k])) piv = i;
+    const double d = H[piv + (size_t)m * k];
+    if (d == 0.0 || !std::isfinite(d)) {
+      char buf[160];
+      std::snprintf(buf, sizeof buf, "projection vectors: H = BV' M^-1 BV is singular (zero pivot in column %d of %d)", k, m);
+      throw hymls::Error(-4, buf);
+    }
+    if (piv != k)
+      for (int j = 0; j < m; j++) {
+        std::swap(H[k + (size_t)m * j], H[piv + (size_t)m * j]);
+        std::swap(G[k + (size_t)m * j], G[piv + (size_t)m * j]);
+      }
+    for (int i = k + 1; i < m; i++) {
+      const double l = H[i + (size_t)m * k] / d;
+      if (l == 0.0) continue;
+      for (int j = k + 1; j < m; j++) H[i + (size_t)m * j] -= l * H[k + (size_t)m * j];
+      for (int j = 0; j < m; j++) G[i + (size_t)m * j] -= l * G[k + (size_t)m * j];
+    }
+  }
+  for (int j = 0; j < m; j++)
+    for (int i = m - 1; i >= 0; i--) {
+      double v = G[i + (size_t)m * j];
+      for (int l = i + 1; l < m; l++) v -= H[i + (size_t)m * l] * G[l + (size_t)m * j];
+      G[i + (size_t)m * j] = v / H[i + (size_t)m * i];
+    }
+  dev::h2d(s->pG, G.data(), (size_t)m * m * sizeof(double));
+  s->p_compute = hymls_mi_num_compute(s->h);
+}
+
+// the checks of a solve with projection vectors, and Z and H where they are missing or stale (counted as ApplyInverse)
+void ready_projection(hymls_mi_solver* s, const HandleView& hv_, Run& R) {
+  HYMLS_CHECK(!hv_.comm->distributed(), -99, "solve with projection vectors: one GPU only (sharded handles are not supported)");
+  HYMLS_CHECK(s->p_n == hv_.top->num_owned(), -2, "the projection vectors do not have the row count of the handle");
+  if (s->p_compute != hymls_mi_num_compute(s->h)) {
+    R.mark(1, true);
+    try { form_projection(s, hv_.top); } catch (...) { R.mark(1, false); throw; }
+    R.mark(1, false);
+  }
+  bind_projection(s, R);
+}
+#endif
+
 void free_buffers(hymls_mi_solver* s) {
 #ifdef HYMLS_MI_LOCKSTEP_SOLVER
   free_lockstep(s);
@@ -707,6 +820,9 @@ int solve_columns(hymls_mi_solver* s, const HandleView& hv_, int bm, const doubl
   }
   R.ws = s->ws;
   R.Vb = s->V;
+#ifdef HYMLS_MI_PROJECTED_SOLVER
+  if (s->pm > 0) ready_projection(s, hv_, R);   // (a bordered solve with projection vectors has been refused before)
+#endif
   s->cols.clear();
   double* v = s->vec;
   R.x = v; R.r = v + s->ld; R.w = v + 2 * s->ld; R.t = v + 3 * s->ld; R.p = v + 4 * s->ld;
@@ -723,7 +839,8 @@ int solve_columns(hymls_mi_solver* s, const HandleView& hv_, int bm, const doubl
   }
 #ifdef HYMLS_MI_LOCKSTEP_SOLVER
   // lock-step columns: groups of `width` consecutive columns (the bordered solve has one right-hand side and ignores it)
-  const int width = bm == 0 ? std::min(s->lockstep, std::max(nvec, 1)) : 1;
+  // and so does a solve with projection vectors: its columns go one after the other
+  const int width = bm == 0 && s->pm == 0 ? std::min(s->lockstep, std::max(nvec, 1)) : 1;
   if (width > 1) {
     ensure_lockstep(s, width, gm);
     Lockstep G{s, L, n, s->ld};
@@ -786,6 +903,10 @@ int solve_columns(hymls_mi_solver* s, const HandleView& hv_, int bm, const doubl
     else if (s->p.initial_vector == 2 && s->have_prev) dev::d2d(R.x, R.prev, n * sizeof(double));
     else dev::zero(R.x, n * sizeof(double));
     R.mark(0, true);
+#ifdef HYMLS_MI_PROJECTED_SOLVER
+    // the start vector in the complement: x0 <- x0 - BV (V' x0) (reference BaseSolver.cpp:339-345)
+    if (R.pm > 0) { R.mark(3, true); dev::kry_oblique_project(n, R.pm, R.pV, R.pld, nullptr, R.pBV, R.pld, R.x, R.x, R.pws); R.mark(3, false); }
+#endif
     int its = 0, restarts = 0;
     double rel = 0;
     bool solved = false;
@@ -844,6 +965,7 @@ int hymls_mi_solver_solve(hymls_mi_solver_t* s, const double* B, int64_t ldb, do
 #ifndef HYMLS_MI_LOCKSTEP_SOLVER
   HYMLS_CHECK(s->lockstep == 1, -99, "this build has no batched Krylov launchers (a test-only simulator without them)");
 #endif
+  HYMLS_CHECK(s->pm == 0 || !hv_.comm->distributed(), -99, "solve with projection vectors: one GPU only (sharded handles are not supported)");
   status = solve_columns(s, hv_, 0, B, ldb, nullptr, X, ldx, nullptr, nvec, on_device);
   SOLVER_END
   return status;
@@ -860,6 +982,7 @@ int hymls_mi_solver_solve_bordered(hymls_mi_solver_t* s, const double* B, const 
   HYMLS_CHECK(hv_.computed && hv_.top, -1, "The preconditioner has not yet been computed.");
   HYMLS_CHECK(!hv_.comm->distributed(), -99, "solve_bordered: one GPU only (sharded handles are not supported)");
   HYMLS_CHECK(B && X, -2, "solve_bordered: null B or X");
+  HYMLS_CHECK(s->pm == 0, -99, "solve_bordered: projection vectors are set (the bordered solve does not combine with them)");
   check_params(s->p);
   const int bm = hv_.top->border_size();
   const int64_t n = hv_.top->num_owned();
@@ -994,6 +1117,162 @@ int hymls_mi_border_product(hymls_mi_t* h, int64_t n, int32_t m, const double* V
     try {
       if (C) { dC = work + (size_t)nb * m; dev::h2d(dC, C, (size_t)m * m * sizeof(double)); }
       dev::kry_border_product(n, m, V, ldv, W, ldw, dC, z, y, ws);
+      dev::sync();
+    } catch (...) { dev::free(work); throw; }
+    dev::free(work);
+#endif
+  } catch (const hymls::Error& e) { *hv.err = e.what(); return e.code; }
+  catch (const std::exception& e) { *hv.err = e.what(); return -3; }
+  return 0;
+}
+
+#ifndef HYMLS_MI_PROJECTED_SOLVER
+#define PROJ_MISSING throw hymls::Error(-99, "this build has no projection kernels (a test-only simulator without them)")
+#endif
+
+int hymls_mi_solver_set_projection(hymls_mi_solver_t* s, int64_t n, int32_t m, const double* V, int64_t ldv, const double* BV,
+                                   int64_t ldbv, int on_device) {
+  if (!s) return -2;
+  SOLVER_BEGIN
+#ifndef HYMLS_MI_PROJECTED_SOLVER
+  (void)n; (void)m; (void)V; (void)ldv; (void)BV; (void)ldbv; (void)on_device;
+  PROJ_MISSING;
+#else
+  if (m == 0 || !V) {              // no projection from the next solve on
+    if (s->p_buf) dev::sync();
+    free_projection(s);
+    return 0;
+  }
+  HYMLS_CHECK(hv_.top, -1, "set_projection needs an initialized handle (its row count)");
+  HYMLS_CHECK(m >= 1 && m <= HYMLS_MI_SOLVER_MAX_PROJECTION, -2, "set_projection: at most 32 projection vectors");
+  HYMLS_CHECK(n == hv_.top->num_owned(), -2, "set_projection: n is not the row count of the handle");
+  HYMLS_CHECK(ldv >= n && (!BV || ldbv >= n), -2, "set_projection: leading dimension smaller than the number of rows");
+  if (s->p_buf) dev::sync();
+  free_projection(s);
+  const bool same = !BV || (BV == V && ldbv == ldv);
+  const int64_t ld = std::max<int64_t>(16, (n + 15) / 16 * 16);
+  const int nb = dev::kry_row_grid(n);
+  const size_t doubles = (size_t)((same ? 2 : 3) * m + 1) * ld + (size_t)m * m + (size_t)nb * m + dev::KRY_PROJ_MAX;
+  try {
+    s->p_buf = (double*)dev::alloc(doubles * sizeof(double));
+  } catch (...) {
+    char buf[192];
+    std::snprintf(buf, sizeof buf, "set_projection: could not allocate %zu bytes of device memory for %d projection vectors "
+                  "(the solver still works without a projection)", doubles * sizeof(double), (int)m);
+    throw hymls::Error(-3, buf);
+  }
+  s->pV = s->p_buf;
+  s->pBV = same ? s->pV : s->pV + (size_t)m * ld;
+  s->pZ = s->pBV + (size_t)m * ld;
+  s->p_tmp = s->pZ + (size_t)m * ld;
+  s->pG = s->p_tmp + ld;
+  s->pws.part = s->pG + (size_t)m * m;
+  s->pws.h1 = s->pws.part + (size_t)nb * m;
+  s->p_same = same; s->p_n = n; s->p_ld = ld;
+  try {
+    for (int j = 0; j < m; j++) {
+      if (on_device) dev::d2d(s->pV + (size_t)j * ld, V + (int64_t)j * ldv, n * sizeof(double));
+      else dev::h2d(s->pV + (size_t)j * ld, V + (int64_t)j * ldv, n * sizeof(double));
+      if (same) continue;
+      if (on_device) dev::d2d(s->pBV + (size_t)j * ld, BV + (int64_t)j * ldbv, n * sizeof(double));
+      else dev::h2d(s->pBV + (size_t)j * ld, BV + (int64_t)j * ldbv, n * sizeof(double));
+    }
+    // the reference's CheckOrthogonal (DenseUtils.cpp:177-199): ||V' BV - I||_inf <= 1e-8, column k of V' BV from the
+    // dots kernel.  (A sharded handle has only this rank's rows here; its solve is refused, so the check is left out)
+    if (!hv_.comm->distributed()) {
+      std::vector<double> M((size_t)m * m);
+      for (int k = 0; k < m; k++) {
+        dev::kry_proj_coeffs(n, m, s->pV, ld, nullptr, s->pBV + (size_t)k * ld, s->pws);
+        dev::d2h(M.data() + (size_t)k * m, s->pws.h1, m * sizeof(double));
+      }
+      double norm = 0.0;
+      for (int i = 0; i < m; i++) {
+        double row = 0.0;
+        for (int k = 0; k < m; k++) row += std::fabs(M[i + (size_t)m * k] - (i == k ? 1.0 : 0.0));
+        norm = std::max(norm, row);
+      }
+      if (!(norm <= 1e-8)) {
+        char buf[160];
+        std::snprintf(buf, sizeof buf, "set_projection: the vectors are not orthogonal, ||V' BV - I||_inf = %.3e (at most 1e-8)", norm);
+        throw hymls::Error(-2, buf);
+      }
+    }
+  } catch (...) {
+    dev::sync();
+    free_projection(s);
+    throw;
+  }
+  s->pm = m;
+#endif
+  SOLVER_END
+  return 0;
+}
+
+int hymls_mi_solver_num_projection(const hymls_mi_solver_t* s) { return s ? s->pm : 0; }
+
+int hymls_mi_solver_set_projection_form(hymls_mi_solver_t* s, int form) {
+  if (!s) return -2;
+  try {
+#ifndef HYMLS_MI_PROJECTED_SOLVER
+    (void)form;
+    PROJ_MISSING;
+#else
+    HYMLS_CHECK(form == 0 || form == 1, -2, "projection form: 0 (folded) or 1 (literal)");
+    s->p_form = form;
+#endif
+  } catch (const hymls::Error& e) { s->err = e.what(); return e.code; }
+  return 0;
+}
+
+int hymls_mi_solver_apply_projected(hymls_mi_solver_t* s, int which, const double* X, double* Y, int on_device) {
+  if (!s) return -2;
+  SOLVER_BEGIN
+#ifndef HYMLS_MI_PROJECTED_SOLVER
+  (void)which; (void)X; (void)Y; (void)on_device;
+  PROJ_MISSING;
+#else
+  HYMLS_CHECK(hv_.computed && hv_.top, -1, "The preconditioner has not yet been computed.");
+  HYMLS_CHECK(s->pm > 0, -2, "apply_projected: no projection vectors are set");
+  HYMLS_CHECK((which == 0 || which == 1) && X && Y, -2, "apply_projected: which is 0 (operator) or 1 (preconditioner); X and Y non-null");
+  const int64_t n = hv_.top->num_owned();
+  Run R{s, hv_.top, hv_.comm, n, s->p_ld, hv_.comm->distributed()};
+  ready_projection(s, hv_, R);
+  double* buf = (double*)dev::alloc((size_t)2 * s->p_ld * sizeof(double));   // staged: X may be Y or host memory
+  try {
+    if (on_device) dev::d2d(buf, X, n * sizeof(double));
+    else dev::h2d(buf, X, n * sizeof(double));
+    if (which == 0) R.matvec(buf, buf + s->p_ld);
+    else R.prec(buf, buf + s->p_ld);
+    if (on_device) { dev::d2d(Y, buf + s->p_ld, n * sizeof(double)); dev::sync(); }
+    else dev::d2h(Y, buf + s->p_ld, n * sizeof(double));
+  } catch (...) { dev::free(buf); throw; }
+  dev::free(buf);
+#endif
+  SOLVER_END
+  return 0;
+}
+
+int hymls_mi_oblique_project(hymls_mi_t* h, int64_t n, int32_t m, const double* Q, int64_t ldq, const double* G, const double* P,
+                             int64_t ldp, const double* x, double* y) {
+  if (!h) return -2;
+  HandleView hv = handle_view(h);
+  try {
+#ifndef HYMLS_MI_PROJECTED_SOLVER
+    (void)n; (void)m; (void)Q; (void)ldq; (void)G; (void)P; (void)ldp; (void)x; (void)y;
+    PROJ_MISSING;
+#else
+    dev::bind(hv.ctx);
+    HYMLS_CHECK(n >= 1 && m >= 1 && m <= HYMLS_MI_SOLVER_MAX_PROJECTION && ldq >= n && ldp >= n && Q && P && x && y, -2,
+                "oblique_project: need n >= 1, 1 <= m <= 32, ldq and ldp >= n and non-null arrays");
+    const int nb = dev::kry_row_grid(n);
+    double* work = (double*)dev::alloc(((size_t)nb * m + (size_t)m * m + dev::KRY_PROJ_MAX) * sizeof(double));
+    dev::KryWork ws{};
+    ws.part = work;
+    ws.h1 = work + (size_t)nb * m + (size_t)m * m;
+    double* dG = nullptr;
+    try {
+      if (G) { dG = work + (size_t)nb * m; dev::h2d(dG, G, (size_t)m * m * sizeof(double)); }
+      dev::kry_oblique_project(n, m, Q, ldq, dG, P, ldp, x, y, ws);
       dev::sync();
     } catch (...) { dev::free(work); throw; }
     dev::free(work);
@@ -1160,6 +1439,7 @@ void hymls_mi_solver_destroy(hymls_mi_solver_t* s) {
     dev::bind(handle_view(s->h).ctx);
     dev::sync();
     free_buffers(s);
+    free_projection(s);
     dev::kry_timer_destroy(s->timer);
   } catch (...) {}
   delete s;

@@ -139,6 +139,28 @@ void kry_dot_mv(int64_t n, const KryVecBatch& b);              // out[0] = a . b
 void kry_cg_xr_mv(int64_t n, const KryVecBatch& b);            // y += s a, r -= s b, out[0] = r . r          (kry_cg_xr: p = a, q = b, x = y)
 void kry_cg_p_mv(int64_t n, const KryVecBatch& b);             // y <- a + s y                                (kry_cg_p: z = a, p = y)
 
+// ---- projection vectors (hymls_mi_solver_set_projection): y = x - P (G (Q' x)), the one primitive behind the projected
+// operator (I - BV V') K (I - V BV') and the projected preconditioner.  P, Q: n x m column-major device arrays (leading
+// dimensions ldp, ldq >= n), 1 <= m <= KRY_PROJ_MAX, dG: device m x m column-major or nullptr (the identity); y may be x.
+// Three kernels, no atomics, every sum in a fixed order that does not depend on the card:
+//   dots    c_j = Q(:, j)' x: one row per thread, grid-stride over kry_row_grid(n) workgroups of 256, the columns in chunks
+//           of KRY_PROJ_CHUNK (one launch per chunk, x is read once per chunk: (m + ceil(m / 8)) n 8 bytes), register
+//           partials, the fixed tree of the workgroup into ws.part[workgroup * m + j]
+//   tail    one workgroup: the partials of each column summed as the other reductions sum them, then
+//           d_j = sum_l G[j + m l] c_l (l ascending; d = c without G), written to ws.h1[0..m)
+//   update  y_i = x_i - sum_j P[i, j] d_j (j ascending, then one subtraction), one pass over the rows for every m:
+//           (m + 2) n 8 bytes
+// kry_proj_coeffs is dots + tail, kry_proj_update the update with the d that is in ws.h1 (the literal preconditioner takes
+// the coefficients from one vector and updates another), kry_oblique_project both.  ws needs part[kry_row_grid(n) * m] and
+// h1[m].  Implemented by krylov_hip.hip and by the test-only tests/krylov_proj_sim; krylov.cpp refers to them only under
+// HYMLS_MI_PROJECTED_SOLVER, because the other simulators have none.
+constexpr int KRY_PROJ_MAX = 32;
+constexpr int KRY_PROJ_CHUNK = 8;
+void kry_proj_coeffs(int64_t n, int32_t m, const double* Q, int64_t ldq, const double* dG, const double* x, const KryWork& ws);
+void kry_proj_update(int64_t n, int32_t m, const double* P, int64_t ldp, const double* x, double* y, const KryWork& ws);
+void kry_oblique_project(int64_t n, int32_t m, const double* Q, int64_t ldq, const double* dG, const double* P, int64_t ldp,
+                         const double* x, double* y, const KryWork& ws);
+
 // phase timing of a solve: events recorded on the stream (the simulator takes host clock readings)
 struct KryTimer;
 KryTimer* kry_timer_create();

@@ -12,6 +12,7 @@
 //   k_kry_reduce*       stage two of every reduction: the partials of one column summed by one workgroup in a fixed
 //                       tree, on the device, so h1 feeds pass B and h2 pass C without a host round trip
 //   k_kry_border_*      the border product of a bordered system [K V; W' C] behind K x: y += V s and the tail W' x + C s
+//   k_kry_proj_*        projection vectors: y = x - P (G (Q' x)), the coefficients in two stages and one update pass
 // plus the vector passes of GMRES and CG.  No atomics anywhere: every result is bitwise reproducible.
 //
 // k_kry_tile and k_kry_rows take the element type of the basis.  With float ("MI Basis Storage" = single) a basis entry
@@ -265,6 +266,77 @@ __global__ void __launch_bounds__(256) k_kry_border_tail(const double* __restric
         for (int l = 0; l < m; l++) v += dC[j + (int64_t)m * l] * z[n + l];
       y[n + j] = v;
     }
+  }
+}
+
+// ---- projection vectors (krylov.hpp: kry_oblique_project), y = x - P (G (Q' x)).  Stage one of the coefficients, MC <=
+// KRY_PROJ_CHUNK columns [c0, c0 + MC) of Q: one row per thread, the MC column reads coalesced across the wave, the thread's
+// partials of Q(:, j)' x in registers, summed per workgroup in the fixed tree into part[workgroup * m + c0 + j]
+template <int MC>
+__global__ void __launch_bounds__(256) k_kry_proj_dots(int64_t n, int m, int c0, const double* __restrict__ Q, int64_t ldq,
+                                                       const double* __restrict__ x, double* __restrict__ part) {
+  __shared__ double red[MC][256];
+  const int t = threadIdx.x;
+  const double* Qc = Q + (int64_t)c0 * ldq;
+  double acc[MC];
+#pragma unroll
+  for (int j = 0; j < MC; j++) acc[j] = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + t; i < n; i += (int64_t)gridDim.x * 256) {
+    const double xi = x[i];
+#pragma unroll
+    for (int j = 0; j < MC; j++) acc[j] += Qc[(int64_t)j * ldq + i] * xi;
+  }
+#pragma unroll
+  for (int j = 0; j < MC; j++) red[j][t] = acc[j];
+  for (int st = 128; st > 0; st >>= 1) {   // block_sum256 for the MC columns at once
+    __syncthreads();
+    if (t < st) {
+#pragma unroll
+      for (int j = 0; j < MC; j++) red[j][t] += red[j][t + st];
+    }
+  }
+  __syncthreads();
+  if (t < MC) part[(int64_t)blockIdx.x * m + c0 + t] = red[t][0];
+}
+// stage two, one workgroup: c_j = the nb partials of column j, summed as k_kry_reduce does; then thread j forms
+// d_j = sum_l G[j + m l] c_l with l ascending (d = c without G)
+__global__ void __launch_bounds__(256) k_kry_proj_tail(const double* __restrict__ part, int nb, int m,
+                                                       const double* __restrict__ dG, double* __restrict__ d) {
+  __shared__ double red[256];
+  __shared__ double cs[KRY_PROJ_MAX];
+  const int t = threadIdx.x;
+  for (int j = 0; j < m; j++) {
+    double s = 0.0;
+    for (int b = t; b < nb; b += 256) s += part[(int64_t)b * m + j];
+    red[t] = s;
+    block_sum256(red);
+    if (t == 0) cs[j] = red[0];
+  }
+  __syncthreads();
+  if (t < m) {
+    double v = cs[t];
+    if (dG) {
+      v = 0.0;
+      for (int l = 0; l < m; l++) v += dG[t + (int64_t)m * l] * cs[l];
+    }
+    d[t] = v;
+  }
+}
+// y_i = x_i - sum_j P[i, j] d_j: one pass over the rows for every m, the coefficients once per workgroup in LDS (every lane
+// reads the same address: a broadcast), the m column reads coalesced across the wave.  y may be x: a thread reads x_i
+// before it writes y_i and touches no other row
+__global__ void __launch_bounds__(256) k_kry_proj_update(int64_t n, int m, const double* __restrict__ P, int64_t ldp,
+                                                         const double* __restrict__ d, const double* x, double* y) {
+  __shared__ double ds[KRY_PROJ_MAX];
+  const int t = threadIdx.x;
+  if (t < m) ds[t] = d[t];
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.x * 256 + t; i < n; i += (int64_t)gridDim.x * 256) {
+    const double* p = P + i;
+    double s = 0.0;
+#pragma unroll 8
+    for (int j = 0; j < m; j++) s += p[(int64_t)j * ldp] * ds[j];
+    y[i] = x[i] - s;
   }
 }
 
@@ -591,6 +663,41 @@ void kry_border_product(int64_t n, int32_t m, const double* V, int64_t ldv, cons
   }
   hipLaunchKernelGGL(k_kry_border_tail, dim3(1), dim3(256), 0, kstream(), ws.part, nb, n, m, dC, z, y);
   kcheck();
+}
+
+template <int MC>
+static void proj_dots(int nb, int64_t n, int32_t m, int c0, const double* Q, int64_t ldq, const double* x, const KryWork& ws) {
+  hipLaunchKernelGGL((k_kry_proj_dots<MC>), dim3(nb), dim3(256), 0, kstream(), n, m, c0, Q, ldq, x, ws.part);
+  kcheck();
+}
+void kry_proj_coeffs(int64_t n, int32_t m, const double* Q, int64_t ldq, const double* dG, const double* x, const KryWork& ws) {
+  if (n < 1 || m < 1 || m > KRY_PROJ_MAX || ldq < n) throw Error(-2, "oblique projection: n >= 1, 1 <= m <= 32, ldq >= n");
+  const int nb = kry_row_grid(n);
+  for (int c0 = 0; c0 < m; c0 += KRY_PROJ_CHUNK) {
+    switch (std::min(KRY_PROJ_CHUNK, m - c0)) {
+      case 1: proj_dots<1>(nb, n, m, c0, Q, ldq, x, ws); break;
+      case 2: proj_dots<2>(nb, n, m, c0, Q, ldq, x, ws); break;
+      case 3: proj_dots<3>(nb, n, m, c0, Q, ldq, x, ws); break;
+      case 4: proj_dots<4>(nb, n, m, c0, Q, ldq, x, ws); break;
+      case 5: proj_dots<5>(nb, n, m, c0, Q, ldq, x, ws); break;
+      case 6: proj_dots<6>(nb, n, m, c0, Q, ldq, x, ws); break;
+      case 7: proj_dots<7>(nb, n, m, c0, Q, ldq, x, ws); break;
+      default: proj_dots<8>(nb, n, m, c0, Q, ldq, x, ws); break;
+    }
+  }
+  hipLaunchKernelGGL(k_kry_proj_tail, dim3(1), dim3(256), 0, kstream(), ws.part, nb, m, dG, ws.h1);
+  kcheck();
+}
+void kry_proj_update(int64_t n, int32_t m, const double* P, int64_t ldp, const double* x, double* y, const KryWork& ws) {
+  if (n < 1 || m < 1 || m > KRY_PROJ_MAX || ldp < n) throw Error(-2, "oblique projection: n >= 1, 1 <= m <= 32, ldp >= n");
+  hipLaunchKernelGGL(k_kry_proj_update, dim3(kry_row_grid(n)), dim3(256), 0, kstream(), n, m, P, ldp, ws.h1, x, y);
+  kcheck();
+}
+void kry_oblique_project(int64_t n, int32_t m, const double* Q, int64_t ldq, const double* dG, const double* P, int64_t ldp,
+                         const double* x, double* y, const KryWork& ws) {
+  if (ldp < n) throw Error(-2, "oblique projection: n >= 1, 1 <= m <= 32, ldp >= n");   // before the first launch
+  kry_proj_coeffs(n, m, Q, ldq, dG, x, ws);
+  kry_proj_update(n, m, P, ldp, x, y, ws);
 }
 
 // ---- lock-step launchers

@@ -9,6 +9,9 @@ load through ``hymls_amd.load_library``.
 ``NativeBorderedSolver(P, params)`` is the native counterpart of ``hymls_amd.BorderedSolver``: the bordered system
 [K V; W' C] [x; s] = [b; t] with the border of P (hymls_mi_solver_solve_bordered).  Its two symbols are bound from a table
 of their own when the first NativeBorderedSolver or ``border_product`` is used.
+
+``NativeSolver.setProjectionVectors(V, W)`` is the reference's ``BaseSolver::setProjectionVectors``: the solve then runs in
+the complement of a small space (hymls_mi_solver_set_projection).  Its symbols are bound from a third table.
 """
 import ctypes as C
 
@@ -70,6 +73,31 @@ _SIG_LOCKSTEP = {
                                                 C.c_void_p]),
 }
 MAX_LOCKSTEP = 4
+
+
+# bound apart from _SIG as well (bind_projection): projection vectors and their building blocks
+_SIG_PROJECTION = {
+    "hymls_mi_solver_set_projection": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                 C.c_int]),
+    "hymls_mi_solver_num_projection": (C.c_int, [C.c_void_p]),
+    "hymls_mi_solver_set_projection_form": (C.c_int, [C.c_void_p, C.c_int]),
+    "hymls_mi_solver_apply_projected": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "hymls_mi_oblique_project": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_int64, C.c_void_p, C.c_void_p]),
+}
+MAX_PROJECTION = 32
+PROJECTION_FORMS = {"folded": 0, "literal": 1}    # "MI Projection Form" (hymls_mi_solver_set_projection_form)
+
+
+def bind_projection(lib):
+    """declare the projection symbols on a loaded library (once); AttributeError if it lacks one"""
+    if not getattr(lib, "_hymls_projection_bound", False):
+        for name, (res, args) in _SIG_PROJECTION.items():
+            f = getattr(lib, name)
+            f.restype = res
+            f.argtypes = args
+        lib._hymls_projection_bound = True
+    return lib
 
 
 def bind_lockstep(lib):
@@ -145,6 +173,24 @@ def lockstep_columns(params):
     return width
 
 
+def projection_form(params):
+    """"MI Projection Form" of the Solver sublist: "folded" (one ApplyInverse per application of the projected
+    preconditioner) or "literal" (the reference's two); None when the key is absent"""
+    form = params.get("Solver", params).get("MI Projection Form")
+    if form is not None and form not in PROJECTION_FORMS:
+        raise ValueError("MI Projection Form must be folded or literal")
+    return form
+
+
+def _colmajor(A):
+    """(pointer, leading dimension, on_device, keep-alive) of an (n, m) numpy array or torch tensor as a column-major block"""
+    if hasattr(A, "data_ptr"):
+        At = A.reshape(A.shape[0], -1).t().contiguous()       # (m, n) row-major: the columns one after the other
+        return At.data_ptr(), At.shape[1], 1, At
+    Ac = np.asfortranarray(np.asarray(A, dtype=np.float64).reshape(np.shape(A)[0], -1))
+    return Ac.ctypes.data, Ac.shape[0], 0, Ac
+
+
 class NativeSolver:
     """K x = b with the library's own Krylov loop; P: a computed hymls_amd.Preconditioner (sharded or not)."""
 
@@ -155,11 +201,14 @@ class NativeSolver:
         self._params = solver_params(params or {})
         bits = basis_bits(params or {})
         width = lockstep_columns(params or {})
+        form = projection_form(params or {})
         ierr = self._lib.hymls_mi_solver_create(C.byref(self._s), P._h, C.byref(self._params))
         if not ierr:
             ierr = self._lib.hymls_mi_solver_set_basis_storage(self._s, bits)
         if not ierr and width != 1:
             ierr = bind_lockstep(self._lib).hymls_mi_solver_set_lockstep(self._s, width)
+        if not ierr and form is not None:
+            ierr = bind_projection(self._lib).hymls_mi_solver_set_projection_form(self._s, PROJECTION_FORMS[form])
         if ierr:
             msg = self._lib.hymls_mi_solver_last_error(self._s).decode() if self._s else "create failed"
             self.close()
@@ -180,6 +229,41 @@ class NativeSolver:
         width = lockstep_columns(params)
         if width != 1 or getattr(self._lib, "_hymls_lockstep_bound", False):
             self._check(bind_lockstep(self._lib).hymls_mi_solver_set_lockstep(self._s, width))
+        form = projection_form(params)
+        if form is not None:
+            self._check(bind_projection(self._lib).hymls_mi_solver_set_projection_form(self._s, PROJECTION_FORMS[form]))
+
+    def setProjectionVectors(self, V, W=None):
+        """the solve works in the complement of span(V): operator (I - W V') K (I - V W'), preconditioner
+        M^-1 (I - W H^-1 W' M^-1) with H = W' M^-1 W, projected start vector (the reference's setProjectionVectors; W is
+        its BV, None means W = V).  V, W: (n, m) numpy arrays or torch device tensors with V' W = I, m <= 32; the solver
+        keeps device copies.  V=None removes the projection.  Pass right-hand sides with V' b = 0."""
+        lib = bind_projection(self._lib)
+        if V is None:
+            self._check(lib.hymls_mi_solver_set_projection(self._s, self._P._n, 0, None, 0, None, 0, 0))
+            return
+        vp, ldv, dev_v, keep_v = _colmajor(V)
+        m = keep_v.shape[0] if dev_v else keep_v.shape[1]
+        wp, ldw, dev_w, keep_w = (None, 0, dev_v, None) if W is None else _colmajor(W)
+        if dev_w != dev_v or (keep_w is not None and tuple(keep_w.shape) != tuple(keep_v.shape)):
+            raise ValueError("V and W must be of one kind (numpy or torch) and one shape")
+        self._check(lib.hymls_mi_solver_set_projection(self._s, ldv, m, vp, ldv, wp, ldw, dev_v))
+
+    def getNumProjection(self):
+        return bind_projection(self._lib).hymls_mi_solver_num_projection(self._s)
+
+    def applyProjected(self, which, X):
+        """one vector through the projected operator (which = 0) or the projected preconditioner (which = 1) as the solve
+        applies them (hymls_mi_solver_apply_projected); X: torch tensor on the device or numpy array of n entries"""
+        lib = bind_projection(self._lib)
+        if hasattr(X, "data_ptr"):
+            Y = X.new_empty(X.shape)
+            self._check(lib.hymls_mi_solver_apply_projected(self._s, which, X.contiguous().data_ptr(), Y.data_ptr(), 1))
+            return Y
+        Xc = np.ascontiguousarray(X, dtype=np.float64)
+        Y = np.empty_like(Xc)
+        self._check(lib.hymls_mi_solver_apply_projected(self._s, which, Xc.ctypes.data, Y.ctypes.data, 0))
+        return Y
 
     def SetTolerance(self, tol):
         self._check(self._lib.hymls_mi_solver_set_tolerance(self._s, float(tol)))
@@ -318,6 +402,19 @@ def border_product(P, n, m, V, ldv, W, ldw, C_, z, y):
     ptr = lambda a: a.data_ptr() if a is not None else None
     ierr = lib.hymls_mi_border_product(P._h, n, m, ptr(V), ldv, ptr(W), ldw, Cm.ctypes.data if Cm is not None else None,
                                        ptr(z), ptr(y))
+    if ierr:
+        raise HymlsError(ierr, lib.hymls_mi_last_error(P._h).decode())
+
+
+def oblique_project(P, n, m, Q, ldq, G, Pm, ldp, x, y):
+    """y = x - Pm (G (Q' x)) (hymls_mi_oblique_project) on device arrays.  Q, Pm (column-major, leading dimensions ldq, ldp),
+    x, y: torch tensors (device memory; host memory with the test-only simulator) or None; y may be x; G: (m, m) array-like
+    or None (the identity)."""
+    lib = bind_projection(P._lib)
+    Gm = None if G is None else np.asfortranarray(np.asarray(G, dtype=np.float64))
+    ptr = lambda a: a.data_ptr() if a is not None else None
+    ierr = lib.hymls_mi_oblique_project(P._h, n, m, ptr(Q), ldq, Gm.ctypes.data if Gm is not None else None, ptr(Pm), ldp,
+                                        ptr(x), ptr(y))
     if ierr:
         raise HymlsError(ierr, lib.hymls_mi_last_error(P._h).decode())
 

@@ -27,6 +27,7 @@ class Solver:
         self._numIter = 0
         self._achieved = float("nan")
         self._prev = None
+        self._pV = self._pW = None
         self.setParameterList(params or {})
 
     # --- reference API
@@ -69,6 +70,46 @@ class Solver:
     def SetTolerance(self, tol):
         self.tol = float(tol)
 
+    def setProjectionVectors(self, V, W=None):
+        """the reference's BaseSolver::setProjectionVectors (src/HYMLS_BaseSolver.cpp:282-306) in the literal form of
+        HYMLS::ProjectedOperator, with torch products: the operator becomes (I - W V') K (I - V W'), the preconditioner
+        M^-1 (I - W H^-1 W' M^-1) with H = W' M^-1 W (two ApplyInverse per application; H is formed by every
+        ApplyInverse of the solver, so it follows a recomputed preconditioner), and the start vector is projected.
+        V, W: (n, m) numpy arrays or torch tensors with V' W = I (W is the reference's BV; None: W = V).  V=None removes
+        the projection.  One GPU.  hymls_amd.NativeSolver has the same method on the device-resident loop."""
+        if V is None:
+            self._pV = self._pW = None
+            return
+        as_t = lambda A: (A if hasattr(A, "data_ptr") else torch.from_numpy(np.ascontiguousarray(A, dtype=np.float64)))
+        Vt = as_t(V).reshape(len(V), -1)
+        Wt = Vt if W is None else as_t(W).reshape(Vt.shape)
+        dev = float(torch.linalg.matrix_norm(Vt.t() @ Wt - torch.eye(Vt.shape[1], dtype=Vt.dtype, device=Vt.device), ord=float("inf")))
+        if not dev <= 1e-8:
+            raise ValueError("Vectors are not orthogonal. The norm is %.3e" % dev)
+        self._pV, self._pW = Vt, Wt
+
+    def _projected_hooks(self, device):
+        """(matvec, prec, project) of the projected system on `device`"""
+        if self._sharded:
+            raise NotImplementedError("projection vectors: one GPU only")
+        V, W = self._pV.to(device), self._pW.to(device)
+        self._pV, self._pW = V, W
+        kmv, pinv = self._matvec, (self._prec if self._prec is not None else (lambda x: x))
+        m = V.shape[1]
+        Z = torch.stack([pinv(W[:, j].contiguous()).clone() for j in range(m)], dim=1)
+        H = (W.t() @ Z).cpu().numpy()
+
+        def matvec(x):
+            t = kmv(x - V @ (W.t() @ x)).clone()
+            return t - W @ (V.t() @ t)
+
+        def prec(x):
+            y = pinv(x).clone()
+            d = np.linalg.solve(H, (W.t() @ y).cpu().numpy())
+            return pinv(x - W @ torch.from_numpy(d).to(device))
+
+        return matvec, prec, lambda x: x - W @ (V.t() @ x)
+
     def getNumIter(self):
         return self._numIter
 
@@ -91,7 +132,15 @@ class Solver:
             x0 = self._prev.clone()
         else:
             x0 = torch.zeros_like(B)
-        x, its, rel = (self._gmres if self.method == "GMRES" else self._cg)(B, x0)
+        if self._pV is not None:
+            saved = (self._matvec, self._prec)
+            self._matvec, self._prec, project = self._projected_hooks(B.device)
+            try:
+                x, its, rel = (self._gmres if self.method == "GMRES" else self._cg)(B, project(x0))
+            finally:
+                self._matvec, self._prec = saved
+        else:
+            x, its, rel = (self._gmres if self.method == "GMRES" else self._cg)(B, x0)
         self._numIter, self._achieved, self._prev = its, rel, x
         if X is not None:
             X.copy_(x)

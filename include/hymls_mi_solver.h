@@ -116,6 +116,48 @@ int hymls_mi_solver_lockstep(const hymls_mi_solver_t* s);
 int hymls_mi_solver_column_result(const hymls_mi_solver_t* s, int v, int* iters, double* achieved_tol, int* restarts,
                                   int* converged);
 
+/* Projection vectors (the reference's HYMLS::BaseSolver::setProjectionVectors with HYMLS::ProjectedOperator): with V and
+ * BV set (n x m, V' BV = I), hymls_mi_solver_solve works in the complement of the space they span, as the correction
+ * equation of Jacobi-Davidson and the deflated solvers need it:
+ *   operator         y = (I - BV V') K (I - V BV') x
+ *   preconditioner   y = M^{-1} (I - BV H^{-1} BV' M^{-1}) x,  H = BV' M^{-1} BV
+ *   start vector     x0 <- x0 - BV (V' x0), after "Zero", "Random" or "Previous" has produced x0
+ * The right-hand side is used as given (the reference hands it to Belos unprojected): pass one with V' b = 0.  GMRES and CG,
+ * both basis storages, left and right preconditioning, restarts, achieved_tol and the per-column results work as without a
+ * projection (CG: with BV = V and symmetric K and M the projected pair is symmetric).  Each projector is one pass for the m
+ * inner products and one for the update, in HIP kernels that sum in a fixed order without atomics.
+ * V, BV: column-major, leading dimensions ldv, ldbv >= n, device pointers if on_device, else host memory; the solver keeps
+ * device copies of its own (one if BV is NULL, which means BV = V).  m = 0 or V NULL removes the projection, and the solver
+ * then takes the path and gives the bits of one that never had it.  -2: m above HYMLS_MI_SOLVER_MAX_PROJECTION, n different
+ * from the handle's row count, a leading dimension below n, or ||V' BV - I||_inf > 1e-8 (the reference's CheckOrthogonal;
+ * the message holds the norm).  Memory: (2 or 3) m + 1 vectors of n doubles (V, BV, Z below, one work vector), allocated by
+ * this call; a failed allocation returns -3 with the bytes asked for in the message and leaves the solver without a
+ * projection.
+ * The first solve after this call forms Z = M^{-1} BV (ApplyInverse in groups of up to four columns), H = BV' Z and, from an
+ * LU factorisation of H with partial pivoting on the host, the dense H^{-1}; a solve after the handle was computed again
+ * (hymls_mi_num_compute has changed) forms them again.  A singular H (zero pivot): -4.  A solve on a sharded handle with a
+ * projection set returns -99 (one GPU), and so does hymls_mi_solver_solve_bordered.  With a projection set the columns of a
+ * solve go one after the other, whatever the lock-step width.  Phase timing: the projectors around K x count as K x
+ * (phase 2), those of the preconditioner and forming Z and H as ApplyInverse (phase 1).
+ * A library built without the projection kernels (a test-only simulator) returns -99 from all five entries below. */
+#define HYMLS_MI_SOLVER_MAX_PROJECTION 32
+int hymls_mi_solver_set_projection(hymls_mi_solver_t* s, int64_t n, int32_t m, const double* V, int64_t ldv, const double* BV,
+                                   int64_t ldbv, int on_device);
+int hymls_mi_solver_num_projection(const hymls_mi_solver_t* s);
+/* form of the projected preconditioner: 0 (default) folded, y = M^{-1} x followed by y -= Z (H^{-1} (BV' y)): one ApplyInverse
+ * per application; 1 literal, the reference's arithmetic: y = M^{-1} x, d = H^{-1} (BV' y), y = M^{-1} (x - BV d): two.  Both
+ * are the same operator in exact arithmetic (M^{-1} (x - BV d) = M^{-1} x - Z d).  Other values: -2. */
+int hymls_mi_solver_set_projection_form(hymls_mi_solver_t* s, int form);
+/* one vector through the projected operator (which = 0) or the projected preconditioner (which = 1) exactly as the solve
+ * applies them (building block, for tests).  X, Y: n entries, device or host as on_device says; Y may be X.  Forms Z and H
+ * if the next solve would.  -2 when no projection is set, -1 before Compute. */
+int hymls_mi_solver_apply_projected(hymls_mi_solver_t* s, int which, const double* X, double* Y, int on_device);
+/* building block (as hymls_mi_border_product): y = x - P (G (Q' x)).  P, Q: n x m column-major device arrays, x, y device
+ * (y may be x); G host, m x m column-major, may be NULL (the identity).  n >= 1, 1 <= m <= HYMLS_MI_SOLVER_MAX_PROJECTION,
+ * ldq, ldp >= n; otherwise -2.  Sums in a fixed order without atomics: the result is bitwise repeatable. */
+int hymls_mi_oblique_project(hymls_mi_t* h, int64_t n, int32_t m, const double* Q, int64_t ldq, const double* G,
+                             const double* P, int64_t ldp, const double* x, double* y);
+
 /* phase timing with events on the stream (adds a synchronisation at the end of every solve while on).
  * which: 0 whole solve, 1 ApplyInverse, 2 K x, 3 orthogonalisation + updates; seconds summed since profiling was
  * switched on. */
