@@ -1,6 +1,7 @@
-"""Kernel lab of the Krylov layer: the vector, reduction and update launchers of krylov.hpp one by one, their batched
-(lock-step) forms, and the multi-vector SpMV of device.hpp.  This module holds the case list, the inputs, the ctypes driver
-of the harness (kry_harness.cpp), the numpy references, the checks and the coverage bookkeeping.
+"""Kernel lab of the Krylov layer: the vector, reduction and update launchers of krylov.hpp one by one, the orthogonalisation
+passes A, B and C pass by pass (both basis types), the projection and border-product launchers, their batched (lock-step)
+forms, and the multi-vector SpMV of device.hpp.  This module holds the case list, the inputs, the ctypes driver of the
+harness (kry_harness.cpp), the numpy references, the checks and the coverage bookkeeping.
 
 The harness is linked twice.  Against the test-only simulators a batched launcher is a loop over the single launcher and
 spmv_mv a loop over spmv, so the simulator run proves the harness, the references, the canaries, the bounds and the
@@ -20,6 +21,8 @@ the factor 2 is the only margin).  m per output:
   r.r of cg_xr                  n, against the extended-precision sum of squares of the r THE LAUNCHER RETURNED: this
                                 isolates the reduction from the element-wise step, which has its own check
   spmv_mv                       per column, the spmv bound of tests/seplab: 2 (len |alpha| eps sum|a x| + eps |beta y|)
+  passes A, B, C, projection    stated with their families below: every coefficient, every stage-one partial against its
+  and border product            own rows, stage two against the returned partials, every row of w / dst / y
 Exact outputs: sub, add, div, scale_by, widen, round_div and round_scale_by round once per output and must equal numpy's
 float64 / float32 arithmetic bit for bit (FP64 division is correctly rounded on both sides; round_div is
 (x / s).astype(float32)).  Where the device scalar is not > 0, scale_by leaves x untouched and round_scale_by writes
@@ -84,6 +87,11 @@ _SIGS = {
     "update_f32": "qipqppq", "scale_by_mv": _MV_SIG, "round_scale_by_mv": _MV_SIG, "widen_mv": _MV_SIG, "dot_mv": _MV_SIG,
     "cg_xr_mv": _MV_SIG, "cg_p_mv": _MV_SIG, "spmv": "ippppqpqqddq", "spmv_mv": "ippppqqpqqqiddq",
 }
+_PASS_SIG = "ippqqpqqpqpqpqqpqqpqp"
+_SIGS.update({"pass_%s_%s" % (ab, t): "qq" + _PASS_SIG for ab in "abc" for t in ("f64", "f32")})
+_SIGS.update({"pass_%s_mv" % ab: "qqii" + _PASS_SIG for ab in "abc"})
+_SIGS.update({"proj_coeffs": "qipqqpqpqpqpqq", "proj_update": "qipqqpqpqqpqq", "oblique_project": "qipqqpqpqqpqpqqpqpqq",
+              "border_product": "qipqqpqqpqpqqpqqpq"})
 _CT = {"q": ctypes.c_int64, "i": ctypes.c_int32, "p": ctypes.c_void_p, "d": ctypes.c_double}
 _loaded = {}
 
@@ -98,6 +106,10 @@ class Lib:
         self.lib.krylab_row_grid.argtypes, self.lib.krylab_row_grid.restype = [ctypes.c_int64], ctypes.c_int32
         self.lib.krylab_spmv_lanes.argtypes, self.lib.krylab_spmv_lanes.restype = [ctypes.c_int32, ctypes.c_int64], ctypes.c_int32
         self.lib.krylab_guard_words.restype = ctypes.c_int64
+        for name in ("krylab_tile_grid", "krylab_tile_grid_f32"):
+            getattr(self.lib, name).argtypes, getattr(self.lib, name).restype = [ctypes.c_int64, ctypes.c_int32], ctypes.c_int32
+        self.tile, self.proj_max, self.proj_chunk, self.border_max, self.border_chunk = (
+            int(getattr(self.lib, "krylab_" + name)()) for name in ("tile", "proj_max", "proj_chunk", "border_max", "border_chunk"))
         self.guard = int(self.lib.krylab_guard_words())
         self.maxgrid, self.kmax, self.lockstep_max = (int(self.lib.krylab_maxgrid()), int(self.lib.krylab_kmax()),
                                                       int(self.lib.krylab_lockstep_max()))
@@ -128,6 +140,10 @@ class Lib:
     def row_grid(self, n):
         """kry_row_grid of krylov.hpp."""
         return int(self.lib.krylab_row_grid(n))
+
+    def tile_grid(self, n, k, f32=False):
+        """kry_tile_grid / kry_tile_grid_f32 of krylov.hpp."""
+        return int((self.lib.krylab_tile_grid_f32 if f32 else self.lib.krylab_tile_grid)(n, k))
 
     def vec_grid(self, n):
         """The vec_grid formula of krylov_hip.hip, from the product's KRY_MAXGRID."""
@@ -307,7 +323,7 @@ def inputs(case, keep=True):
 
 
 def run_case(lib, case):
-    assert lib.maxgrid == MAXGRID
+    assert lib.maxgrid == MAXGRID and (lib.kmax, lib.guard, lib.tile) == (KMAX, GUARD, TILE)
     return FAMILIES[case.family][1](lib, case, inputs(case))
 
 
@@ -776,12 +792,467 @@ def spmv_check(case, inp, out):
     return fails, worst
 
 
+# ---- the orthogonalisation passes A, B, C: single (both basis types) and batched
+# Bounds (the rule at the top), per output:
+#   h1[j] of pass A, h2[j] of pass B     m = n          terms V_ij w_i (pass B: the w the launcher returned)
+#   a stage-one partial                  m = its rows   the rows of the tiles b, b + grid, ... (grid: the product's own
+#                                                       kry_tile_grid[_f32](n, k), or kry_row_grid(n) in pass C)
+#   stage two                            m = grid       against the extended-precision sum of the returned partials
+#   a row of w (pass B) or dst (pass C)  m = k + 1      terms w_i and V_ij h_j
+#   out[k + 1] of pass C                 m = n          against the sum of squares of the returned dst
+# Exact: out[j] = h1[j] + h2[j] of the returned h2 (one add), out[k] = sqrt(out[k + 1]) (one ulp allowed, the distance is
+# recorded in SQRT_ULPS), every input keeps its bits, n = 0 gives +0.0 everywhere.
+KMAX, GUARD, TILE = 256, 1024, 64       # KRY_KMAX, the harness's guard words, KRY_TILE; run_case() asserts that the library agrees
+PASS_MODES = ("dst", "w", "basis")      # pass C: a separate destination, dst = w, dst = column k of the same basis array
+SQRT_ULPS = {}                          # case (and column) -> |out[k] - sqrt(out[k + 1])| in ulps, filled by the checks
+
+
+def strided_cols(V, n, k, ld):
+    """The k columns of a flat basis as a (k, n) view."""
+    if k == 0:
+        return np.zeros((0, n), V.dtype)
+    return np.lib.stride_tricks.as_strided(V, shape=(k, n), strides=(ld * V.itemsize, V.itemsize), writeable=False)
+
+
+def group_sums(terms, rows_per, grid, dtype=LD):
+    """terms (c, n) -> (c, grid): entry b sums the rows of the blocks b, b + grid, b + 2 grid, ... of rows_per rows each."""
+    c, n = terms.shape
+    nblk = -(-n // rows_per)
+    trips = max(1, -(-nblk // grid))
+    pad = np.zeros((c, trips * grid * rows_per), dtype)
+    pad[:, :n] = terms
+    return pad.reshape(c, trips, grid, rows_per).sum(axis=(1, 3))
+
+
+def plus_zero(name, a, fails):
+    if np.any(a != 0.0) or np.any(np.signbit(a)):
+        fails.append("%s: n = 0 must give +0.0" % name)
+
+
+def chk_grouped(name, terms, rows_per, grid, part, total, fails):
+    """The dots of one pass: total[j] against the sum of terms[j] (m = n), the partials part[b, j] against their rows, and
+    total[j] against the returned partials (stage two, m = grid).  terms: a function (j0, j1) -> (j1 - j0, n) longdouble."""
+    k, worst = len(total), 0.0
+    n = terms(0, 1).shape[1]
+    rows = group_sums(np.ones((1, n)), rows_per, grid, np.float64)[0]
+    part = part.reshape(grid, k)
+    for j0 in range(0, k, 16):
+        j1 = min(k, j0 + 16)
+        t = terms(j0, j1)
+        ta = np.abs(t)
+        worst = max(worst, _bounded(name, total[j0:j1], t.sum(axis=1), 2 * n * EPS * ta.sum(axis=1).astype(np.float64), fails))
+        worst = max(worst, _bounded(name + " (a partial against its rows)", part[:, j0:j1].T, group_sums(t, rows_per, grid),
+                                    2 * rows * EPS * group_sums(ta, rows_per, grid).astype(np.float64), fails))
+    if np.all(np.isfinite(part)):
+        pl = part.astype(LD)
+        worst = max(worst, _bounded(name + " (stage two over its partials)", total, pl.sum(axis=0),
+                                    2 * grid * EPS * np.abs(pl).sum(axis=0).astype(np.float64), fails))
+    if n == 0:
+        plus_zero(name, total, fails)
+        plus_zero(name + " (partials)", part, fails)
+    return worst
+
+
+def chk_rows(name, cols, h, w0, got, fails):
+    """got = w0 - V h row by row, m = k + 1."""
+    k, n = cols.shape
+    s, sa = np.zeros(n, LD), np.zeros(n, LD)
+    for j0 in range(0, k, 16):
+        t = cols[j0:j0 + 16].astype(LD) * h[j0:j0 + 16].astype(LD)[:, None]
+        s += t.sum(axis=0)
+        sa += np.abs(t).sum(axis=0)
+    return _bounded(name, got, w0.astype(LD) - s, 2 * (k + 1) * EPS * (np.abs(w0) + sa.astype(np.float64)), fails)
+
+
+def ulps(a, b):
+    """The distance of two finite non-negative doubles in units of the last place."""
+    return abs(int(np.float64(a).view(np.int64)) - int(np.float64(b).view(np.int64)))
+
+
+def chk_pass_column(which, name, n, k, ld, col, got, grid, fails):
+    """The reference checks of one column of one pass.  col: its inputs V, w, h1, h2; got: the payloads part, h1, h2, out, w,
+    dst the launcher returned."""
+    cols = strided_cols(col["V"], n, k, ld)
+    dots = lambda w: (lambda j0, j1: cols[j0:j1].astype(LD) * w.astype(LD))
+    if which == "a":
+        return chk_grouped(name + " h1", dots(col["w"]), TILE, grid, got["part"], got["h1"], fails)
+    if which == "b":
+        worst = chk_rows(name + " w", cols, col["h1"], col["w"], got["w"], fails)
+        if np.all(np.isfinite(got["w"])):
+            worst = max(worst, chk_grouped(name + " h2", dots(got["w"]), TILE, grid, got["part"], got["h2"], fails))
+        _exact(name + " out = h1 + h2", got["out"][:k], col["h1"] + got["h2"], fails)
+        return worst
+    worst = chk_rows(name + " dst", cols, col["h2"], col["w"], got["dst"], fails)
+    if np.all(np.isfinite(got["dst"])):
+        sq = lambda j0, j1: got["dst"].astype(LD)[None, :] ** 2
+        worst = max(worst, chk_grouped(name + " norm^2", sq, 256, grid, got["part"], got["out"][k + 1:k + 2], fails))
+    nrm, ss = got["out"][k], got["out"][k + 1]
+    if not (np.isfinite(nrm) and np.isfinite(ss) and ss >= 0.0 and nrm >= 0.0):
+        fails.append("%s: norm %r of norm^2 %r" % (name, nrm, ss))
+    else:
+        SQRT_ULPS[name] = ulps(nrm, np.sqrt(ss))
+        if SQRT_ULPS[name] > 1:
+            fails.append("%s: out[k] is %d ulps from the restatement sqrt(out[k + 1])" % (name, SQRT_ULPS[name]))
+        if n == 0 and np.signbit(nrm):
+            fails.append("%s: n = 0 must give +0.0" % name)
+    return worst
+
+
+def orth_params(case):
+    """(pass, batched, f32, n, ld, mode, the k of every column, nb as given)."""
+    p, batched = case.p, case.family.endswith("_mv")
+    ks = tuple(p["ks"]) if batched else (p["k"],)
+    return case.family[5], batched, bool(p["f32"]), p["n"], p["ld"], p.get("mode", 0), ks, p["nb"] if batched else 1
+
+
+def orth_inputs(case):
+    which, batched, f32, n, ld, mode, ks, nb = orth_params(case)
+    rng, inp = case.rng(), {}
+    for c, k in enumerate(ks):
+        V = vec(rng, (k - 1) * ld + n if k > 0 else 0)
+        inp["V%d" % c] = V.astype(np.float32) if f32 else V
+        inp["w%d" % c], inp["h1%d" % c], inp["h2%d" % c] = vec(rng, n), vec(rng, min(k, KMAX)), vec(rng, min(k, KMAX))
+    return inp
+
+
+def orth_column(inp, c):
+    return {key: inp["%s%d" % (key, c)] for key in ("V", "w", "h1", "h2")}
+
+
+def orth_valid(ks, nb, batched):
+    return all(1 <= k <= KMAX for k in ks) and (not batched or 1 <= nb <= 4)
+
+
+def spread(lengths, start):
+    """Element offsets of regions of the given lengths in one flat array: the first at `start`, the gap behind region c is
+    1 + c elements, so odd and even starts both occur.  Returns (offsets, total length)."""
+    off, pos = [], start
+    for c, L in enumerate(lengths):
+        off.append(pos)
+        pos += L + 1 + c
+    return off, (off[-1] + lengths[-1] if lengths else 0)
+
+
+def orth_layout(which, batched, n, ld, mode, ks, grids):
+    """The offset table (7 kinds x 4 columns) and the payload length of every kind.  The scratch of a column is as long as
+    its own defined set (tighter than the solver's allocation), so a partial too many lands on the canary."""
+    start = 1 if batched else 0
+    vlen = [(k * ld + n if mode == 2 else ((k - 1) * ld + n if k > 0 else 0)) for k in ks]
+    plen = [(g * k if which in "ab" else g) if 1 <= k <= KMAX else 8 for k, g in zip(ks, grids)]
+    tab, tot = np.zeros((7, 4), np.int64), np.zeros(7, np.int64)
+    for kind, lens in enumerate((vlen, [n] * len(ks), [n] * len(ks), plen, [KMAX] * len(ks), [KMAX] * len(ks), [KMAX + 2] * len(ks))):
+        off, tot[kind] = spread(lens, start)
+        tab[kind, :len(off)] = off
+    return tab, tot
+
+
+def canary_buffer(n_words):
+    return np.full(n_words, CANARY, dtype=np.uint64).view(np.float64)
+
+
+def orth_initial(which, batched, f32, n, ld, mode, ks, inp, tab, tot):
+    """The buffers as the launcher finds them: canary everywhere except the caller's content (the basis columns, w, h1, h2)."""
+    buf = {key: canary_buffer(int(tot[kind]) + GUARD) for kind, key in ((1, "W"), (3, "P"), (4, "H1"), (5, "H2"), (6, "O"))}
+    if which == "c" and mode == 0:
+        buf["DST"] = canary_buffer(int(tot[2]) + GUARD)
+    if mode == 2:
+        buf["V"] = canary_buffer(int(tot[0]) + GUARD)
+    else:
+        buf["V"] = np.full(int(tot[0]), np.nan, dtype=np.float32 if f32 else np.float64)    # a read of a gap is a NaN in the result
+    for c, k in enumerate(ks):
+        V = inp["V%d" % c]
+        if mode == 2:
+            for j in range(k):
+                buf["V"][tab[0, c] + j * ld:tab[0, c] + j * ld + n] = V[j * ld:j * ld + n]
+        else:
+            buf["V"][tab[0, c]:tab[0, c] + len(V)] = V
+        buf["W"][tab[1, c]:tab[1, c] + n] = inp["w%d" % c]
+        if which != "a":                                   # pass A finds the canary in h1: it must write all of h1[0:k)
+            buf["H1"][tab[4, c]:tab[4, c] + len(inp["h1%d" % c])] = inp["h1%d" % c]
+        if which != "b":
+            buf["H2"][tab[5, c]:tab[5, c] + len(inp["h2%d" % c])] = inp["h2%d" % c]
+    return buf
+
+
+def orth_call(lib, which, batched, f32, n, ld, mode, ks, nb, inp):
+    """One launch.  Returns the whole buffers, the error code, the own grid of every column and the layout."""
+    grids = [(lib.tile_grid(n, k, f32) if which in "ab" else lib.row_grid(n)) if 1 <= k <= KMAX else 1 for k in ks]
+    tab, tot = orth_layout(which, batched, n, ld, mode, ks, grids)
+    buf = orth_initial(which, batched, f32, n, ld, mode, ks, inp, tab, tot)
+    K = np.zeros(4, np.int32)
+    K[:len(ks)] = ks
+    init = lambda kind: int(tot[kind]) * 8
+    dst = buf.get("DST")
+    name = "pass_%s_mv" % which if batched else "pass_%s_%s" % (which, "f32" if f32 else "f64")
+    code, msg = lib.call(name, *((n, ld) + ((nb, int(f32)) if batched else ()) + (
+        mode, K, buf["V"], int(tot[0]), words(buf["V"]) if mode == 2 else 0, buf["W"], init(1), words(buf["W"]), dst,
+        words(dst) if dst is not None else 0, buf["P"], words(buf["P"]), buf["H1"], init(4), words(buf["H1"]), buf["H2"], init(5),
+        words(buf["H2"]), buf["O"], words(buf["O"]), np.ascontiguousarray(tab.ravel()))))
+    res = {key: v for key, v in buf.items() if key != "V" or mode == 2}
+    res.update(code=np.array([code]), grid=i64(grids), tab=tab, tot=tot)
+    return res
+
+
+def orth_payloads(which, n, ld, mode, ks, res):
+    """Per column, what the pass defines: its slices of the returned buffers."""
+    tab, cols = res["tab"], []
+    for c, k in enumerate(ks):
+        g = int(res["grid"][c])
+        got = {"part": res["P"][tab[3, c]:tab[3, c] + (g * k if which in "ab" else g)], "h1": res["H1"][tab[4, c]:tab[4, c] + k],
+               "h2": res["H2"][tab[5, c]:tab[5, c] + k], "out": res["O"][tab[6, c]:tab[6, c] + k + 2], "w": res["W"][tab[1, c]:tab[1, c] + n]}
+        if which == "c":
+            got["dst"] = (res["DST"][tab[2, c]:tab[2, c] + n] if mode == 0 else got["w"] if mode == 1
+                          else res["V"][tab[0, c] + k * ld:tab[0, c] + k * ld + n])
+        cols.append(got)
+    return cols
+
+
+ORTH_DEFINED = {"a": ("part", "h1"), "b": ("part", "h2", "out", "w"), "c": ("part", "out", "dst")}    # compared with the single launch
+
+
+def orth_outputs(which, k, got):
+    """The defined outputs of a column, out cut to its defined part."""
+    res = {key: got[key] for key in ORTH_DEFINED[which]}
+    if "out" in res:
+        res["out"] = got["out"][:k] if which == "b" else got["out"][k:k + 2]
+    return res
+
+
+def orth_run(lib, case, inp):
+    which, batched, f32, n, ld, mode, ks, nb = orth_params(case)
+    res = orth_call(lib, which, batched, f32, n, ld, mode, ks, nb, inp)
+    if int(res["code"][0]) != 0:
+        return res
+    if not batched and which == "c":                       # two calls: the same bits
+        again = orth_call(lib, which, batched, f32, n, ld, mode, ks, nb, inp)
+        res["same_again"] = np.array([all(same_bits(res[key], again[key]) for key in again)])
+    if batched:                                            # the single launcher of the same library on the operands of column c
+        got = orth_payloads(which, n, ld, mode, ks, res)
+        for c, k in enumerate(ks):
+            one_inp = {"%s0" % key: v for key, v in orth_column(inp, c).items()}
+            one = orth_call(lib, which, False, f32, n, ld, mode, (k,), 1, one_inp)
+            if int(one["code"][0]) != 0:
+                raise RuntimeError("single launch of column %d: error %d" % (c, int(one["code"][0])))
+            single = orth_outputs(which, k, orth_payloads(which, n, ld, mode, (k,), one)[0])
+            res["same_as_single%d" % c] = np.array([same_bits(digest(single[key]), digest(v))
+                                                    for key, v in orth_outputs(which, k, got[c]).items()])
+    return res
+
+
+def unchanged(buf, init, defined, what, fails):
+    """Every word of buf outside the defined elements has the bits the launcher found there."""
+    raw = np.uint64 if buf.dtype.itemsize == 8 else np.uint32
+    mask = np.zeros(buf.size, bool)
+    for a, b in defined:
+        mask[a:b] = True
+    bad = np.flatnonzero((buf.view(raw) != init.view(raw)) & ~mask)
+    if bad.size:
+        fails.append("%s: written outside its output set at %s (%d words)" % (what, bad[:3], bad.size))
+
+
+def orth_check(case, inp, out):
+    which, batched, f32, n, ld, mode, ks, nb = orth_params(case)
+    fails, worst, code = [], 0.0, int(out["code"][0])
+    tab, tot = out["tab"], out["tot"]
+    init = orth_initial(which, batched, f32, n, ld, mode, ks, inp, tab, tot)
+    valid = orth_valid(ks, nb, batched)
+    sets = {key: [] for key in ("W", "DST", "V", "P", "H1", "H2", "O")}
+    if valid:
+        for c, k in enumerate(ks):
+            g = int(out["grid"][c])
+            sets["P"].append((tab[3, c], tab[3, c] + (g * k if which in "ab" else g)))
+            if which == "a":
+                sets["H1"].append((tab[4, c], tab[4, c] + k))
+            elif which == "b":
+                sets["H2"].append((tab[5, c], tab[5, c] + k))
+                sets["O"].append((tab[6, c], tab[6, c] + k))
+                sets["W"].append((tab[1, c], tab[1, c] + n))
+            else:
+                sets["O"].append((tab[6, c] + k, tab[6, c] + k + 2))
+                sets[("DST", "W", "V")[mode]].append((tab[(2, 1, 0)[mode], c] + (k * ld if mode == 2 else 0),
+                                                      tab[(2, 1, 0)[mode], c] + (k * ld if mode == 2 else 0) + n))
+    for key in sets:
+        if key in out:
+            unchanged(out[key], init[key], sets[key], {"W": "w", "DST": "dst", "V": "the basis", "P": "part", "H1": "h1", "H2": "h2",
+                                                       "O": "out"}[key], fails)
+    if not valid:
+        if code != -2:
+            fails.append("k = %s, nb = %d: error %d instead of -2" % (ks, nb, code))
+        return fails, 0.0
+    if code != 0:
+        return fails + ["error %d" % code], 0.0
+    got = orth_payloads(which, n, ld, mode, ks, out)
+    for c, k in enumerate(ks):
+        name = "%s column %d" % (case.name, c) if batched else case.name
+        worst = max(worst, chk_pass_column(which, name, n, k, ld, orth_column(inp, c), got[c], int(out["grid"][c]), fails))
+        if batched:
+            for key, same in zip(orth_outputs(which, k, got[c]), out["same_as_single%d" % c]):
+                if not same:
+                    fails.append("column %d: %s differs from the single launch" % (c, key))
+    if "same_again" in out and not bool(out["same_again"][0]):
+        fails.append("two calls differ")
+    return fails, worst
+
+
+# ---- projection vectors and the border product
+# proj_coeffs: d = G (Q' x) in ws.h1.  Without G d_j is a sum of n terms; with G the bound E_j = (n + m + 1) u (|G| a)_j,
+# a_l = sum_i |Q_il x_i|, derived in check_oblique_project of tests/native_projected_cases.py, and so is the row bound of
+# oblique_project, (m + 2) u (|x_i| + sum_j |P_ij| (|d_j| + E_j)) + sum_j |P_ij| E_j.  A partial is checked against its rows
+# (256 per workgroup, kry_row_grid(n) workgroups); stage two: d_j = sum_l G_jl sum_b part[b, l], where every term passes
+# through at most grid + m + 1 roundings.  proj_update: m + 1 terms per row.  border_product: m + 1 terms per row, n + m per
+# entry of the tail.
+def flat_cols(rng, n, m, ld):
+    """An n x m column-major array with leading dimension ld, exactly (m - 1) ld + n entries; the padding holds NaN."""
+    a = np.full(max(0, (m - 1) * ld + n) if m > 0 else 0, np.nan)
+    for j in range(m):
+        a[j * ld:j * ld + n] = vec(rng, n)
+    return a
+
+
+def proj_refused(case):
+    p = case.p
+    return p["n"] < 1 or p["m"] < 1 or p["m"] > 32 or p["ld"] < p["n"]
+
+
+def proj_inputs(case):
+    rng, n, m, ld = case.rng(), case.p["n"], case.p["m"], case.p["ld"]
+    inp = {"Q": flat_cols(rng, n, m, ld), "P": flat_cols(rng, n, m, ld), "x": vec(rng, n), "G": vec(rng, m * m), "d": vec(rng, min(m, 32))}
+    if case.family == "border_product":
+        inp["z"], inp["y"] = vec(rng, n + m), vec(rng, n)
+    return inp
+
+
+def proj_run(lib, case, inp):
+    n, m, ld, F, res = case.p["n"], case.p["m"], case.p["ld"], case.family, {}
+    grid = lib.row_grid(n)
+    res["grid"] = i64([grid])
+    npart = grid * m if not proj_refused(case) else 8
+    for v in (0, 1):                                       # proj_coeffs, oblique_project: without and with G; proj_update: out of
+        part, h1 = lib.out(npart), lib.out(KMAX)           # place and in place; border_product: without and with C
+        G = inp["G"] if v else None
+        if F == "proj_coeffs":
+            code, _ = lib.call("proj_coeffs", n, m, inp["Q"], len(inp["Q"]), ld, G, m * m, inp["x"], n, part, words(part), h1, 0, words(h1))
+            res.update({"P%d" % v: part, "H%d" % v: h1})
+        elif F == "proj_update":
+            h1[:len(inp["d"])] = inp["d"]
+            y = lib.out(n, init=inp["x"] if v else None)
+            code, _ = lib.call("proj_update", n, m, inp["P"], len(inp["P"]), ld, None if v else inp["x"], n, y, n * 8 if v else 0, words(y),
+                               h1, len(inp["d"]) * 8, words(h1))
+            res.update({"Y%d" % v: y, "H%d" % v: h1})
+        elif F == "oblique_project":
+            ys = []
+            for inplace in (0, 1):
+                part, h1 = lib.out(npart), lib.out(KMAX)
+                y = lib.out(n, init=inp["x"] if inplace else None)
+                code, _ = lib.call("oblique_project", n, m, inp["Q"], len(inp["Q"]), ld, G, m * m, inp["P"], len(inp["P"]), ld,
+                                   None if inplace else inp["x"], n, y, n * 8 if inplace else 0, words(y), part, words(part), h1, 0, words(h1))
+                ys.append((y, part, h1))
+            res.update({"Y%d" % v: ys[0][0], "P%d" % v: ys[0][1], "H%d" % v: ys[0][2],
+                        "inplace_same%d" % v: np.array([all(same_bits(a, b) for a, b in zip(ys[0], ys[1]))])})
+        else:
+            y, z = lib.out(n + m, init=inp["y"]), lib.out(n + m, init=inp["z"])
+            code, _ = lib.call("border_product", n, m, inp["Q"], len(inp["Q"]), ld, inp["P"], len(inp["P"]), ld, G, m * m, z, (n + m) * 8,
+                               words(z), y, n * 8, words(y), part, words(part))
+            res.update({"Y%d" % v: y, "Z%d" % v: z, "P%d" % v: part})
+        res["code%d" % v] = np.array([code])
+    return res
+
+
+def proj_cols(a, n, m, ld):
+    return strided_cols(a, n, m, ld)
+
+
+def proj_check(case, inp, out):
+    n, m, ld, F = case.p["n"], case.p["m"], case.p["ld"], case.family
+    fails, worst, grid = [], 0.0, int(out["grid"][0])
+    for v in (0, 1):
+        code, nm = int(out["code%d" % v][0]), "%s (%s)" % (case.name, ("plain", "second form")[v])
+        start = {"H": canary_buffer(KMAX + GUARD)}
+        if F == "proj_update":
+            start["H"][:len(inp["d"])] = inp["d"]
+        if F == "border_product":
+            start["Z"], start["Y"] = canary_buffer(n + m + GUARD), canary_buffer(n + m + GUARD)
+            start["Z"][:n + m], start["Y"][:n] = inp["z"], inp["y"]
+        else:
+            start["Y"] = canary_buffer(n + GUARD)
+            if F == "proj_update" and v:
+                start["Y"][:n] = inp["x"]
+        if "P%d" % v in out:
+            start["P"] = canary_buffer(words(out["P%d" % v]))
+        ok = not proj_refused(case) and code == 0
+        sets = {"H": [(0, m)] if ok and F in ("proj_coeffs", "oblique_project") else [], "P": [(0, grid * m)] if ok else [], "Z": [],
+                "Y": [(0, n + m if F == "border_product" else n)] if ok else []}
+        for key in ("H", "P", "Z", "Y"):
+            if "%s%d" % (key, v) in out:
+                unchanged(out["%s%d" % (key, v)], start[key], sets[key], {"H": "h1", "P": "part", "Z": "z", "Y": "y"}[key], fails)
+        if proj_refused(case):
+            if code != -2:
+                fails.append("%s: error %d instead of -2" % (nm, code))
+            continue
+        if code != 0:
+            fails.append("%s: error %d" % (nm, code))
+            continue
+        Q, P, xl = proj_cols(inp["Q"], n, m, ld).astype(LD), proj_cols(inp["P"], n, m, ld).astype(LD), inp["x"].astype(LD)
+        G = inp["G"].reshape(m, m).T if v else None        # column-major: G[j, l] = flat[j + m l]
+        if F == "proj_update":
+            t = P * inp["d"].astype(LD)[:, None]
+            worst = max(worst, _bounded(nm + " y", out["Y%d" % v][:n], xl - t.sum(axis=0),
+                                        2 * (m + 1) * EPS * (np.abs(inp["x"]) + np.abs(t).sum(axis=0).astype(np.float64)), fails))
+            continue
+        if F == "border_product":
+            z, zl = out["Z%d" % v][:n + m], inp["z"].astype(LD)
+            t = Q * zl[n:][:, None]                        # V s
+            worst = max(worst, _bounded(nm + " rows", out["Y%d" % v][:n], inp["y"].astype(LD) + t.sum(axis=0),
+                                        2 * (m + 1) * EPS * (np.abs(inp["y"]) + np.abs(t).sum(axis=0).astype(np.float64)), fails))
+            wx = P * zl[:n]                                # W' x
+            cs = (G.astype(LD) * zl[n:][None, :]) if v else np.zeros((m, m), LD)
+            worst = max(worst, _bounded(nm + " tail", out["Y%d" % v][n:n + m], wx.sum(axis=1) + cs.sum(axis=1),
+                                        2 * (n + m) * EPS * (np.abs(wx).sum(axis=1) + np.abs(cs).sum(axis=1)).astype(np.float64), fails))
+            part = out["P%d" % v][:grid * m].reshape(grid, m)
+            rows = group_sums(np.ones((1, n)), 256, grid, np.float64)[0]
+            worst = max(worst, _bounded(nm + " (a partial against its rows)", part.T, group_sums(wx, 256, grid),
+                                        2 * rows * EPS * group_sums(np.abs(wx), 256, grid).astype(np.float64), fails))
+            continue
+        # the coefficients
+        t = Q * xl
+        a = np.abs(t).sum(axis=1).astype(np.float64)
+        c = t.sum(axis=1)
+        d = G.astype(LD) @ c if v else c
+        E = (n + m + 1) * EPS * ((np.abs(G) if v else np.eye(m)) @ a)
+        got_d = out["H%d" % v][:m]
+        worst = max(worst, _bounded(nm + " d", got_d, d, E if v else 2 * n * EPS * a, fails))
+        part = out["P%d" % v][:grid * m].reshape(grid, m)
+        rows = group_sums(np.ones((1, n)), 256, grid, np.float64)[0]
+        worst = max(worst, _bounded(nm + " (a partial against its rows)", part.T, group_sums(t, 256, grid),
+                                    2 * rows * EPS * group_sums(np.abs(t), 256, grid).astype(np.float64), fails))
+        if np.all(np.isfinite(part)):
+            pl = part.astype(LD)
+            Gl, Ga = (G.astype(LD), np.abs(G)) if v else (np.eye(m).astype(LD), np.eye(m))
+            worst = max(worst, _bounded(nm + " (stage two over its partials)", got_d, Gl @ pl.sum(axis=0),
+                                        2 * (grid + m + 1) * EPS * (Ga @ np.abs(pl).sum(axis=0).astype(np.float64)), fails))
+        if F == "oblique_project":
+            s, sa, se = np.zeros(n, LD), np.zeros(n), np.zeros(n)
+            for j in range(m):
+                s += P[j] * d[j]
+                sa += np.abs(P[j]).astype(np.float64) * (float(abs(d[j])) + E[j])
+                se += np.abs(P[j]).astype(np.float64) * E[j]
+            worst = max(worst, _bounded(nm + " y", out["Y%d" % v][:n], xl - s, (m + 2) * EPS * (np.abs(inp["x"]) + sa) + se, fails))
+            if not bool(out["inplace_same%d" % v][0]):
+                fails.append("%s: y = x gives other bits than the out-of-place call" % nm)
+    return fails, worst
+
+
 EXACT_OPS = ("sub", "add", "div", "scale_by", "widen", "round_div", "round_scale_by")
 FAMILIES = {op: (ev_inputs, ev_run, ev_check) for op in EXACT_OPS}
 FAMILIES.update({"dot": (dot_inputs, dot_run, dot_check), "cg_xr": (cg_inputs, cg_run, cg_check), "cg_p": (cg_inputs, cg_run, cg_check),
                  "update": (upd_inputs, upd_run, upd_check), "spmv_mv": (spmv_inputs, spmv_run, spmv_check)})
 FAMILIES.update({op: (mv_inputs, mv_run, mv_check) for op in MV_OPS})
-BOUNDED_FAMILIES = ("dot", "cg_xr", "cg_p", "update", "dot_mv", "cg_xr_mv", "cg_p_mv", "spmv_mv")
+PASS_OPS = ("pass_a", "pass_b", "pass_c")
+PASS_MV_OPS = ("pass_a_mv", "pass_b_mv", "pass_c_mv")
+PROJ_OPS = ("proj_coeffs", "proj_update", "oblique_project", "border_product")
+FAMILIES.update({op: (orth_inputs, orth_run, orth_check) for op in PASS_OPS + PASS_MV_OPS})
+FAMILIES.update({op: (proj_inputs, proj_run, proj_check) for op in PROJ_OPS})
+BOUNDED_FAMILIES = ("dot", "cg_xr", "cg_p", "update", "dot_mv", "cg_xr_mv", "cg_p_mv", "spmv_mv") + PASS_OPS + PASS_MV_OPS + PROJ_OPS
 BITWISE_FAMILIES = EXACT_OPS + ("scale_by_mv", "round_scale_by_mv", "widen_mv")
 
 # ------------------------------------------------------------------ the cases
@@ -801,6 +1272,63 @@ CASES = (
     [Case("%s_n257_nb%d" % (op, nb), op, n=257, nb=nb) for op in MV_OPS for nb in (0, 5)] +
     [Case("spmv_mv_%d_L%d_nv%d" % (n, L, nv), "spmv_mv", nrows=n, lanes=L, nv=nv) for n in (1, 63, 65, 257) for L in (1, 2, 4, 8)
      for nv in (1, 2, 3, 4, 5, 6, 7, 9)]
+)
+
+# ---- the orthogonalisation passes, the projection and the border product.  The shapes are the smallest that reach each
+# branch; coverage() checks them against the product's own grid functions
+PROJ_M = (1, 2, 7, 8, 9, 16, 17, 32)
+PROJ_N = (1, 255, 257, 4099)
+MV_KS = (5, 256, 3, 31)                                    # the k of the columns of a batched launch: the largest is not column 0
+
+
+def _pad(i):
+    return 5 if i % 2 else 0
+
+
+def _ty(f32):
+    return "f32" if f32 else "f64"
+
+
+def tile_shapes(f32):
+    """(n, k) of passes A and B.  The k where the workgroups per CU change: 30 | 31 and 148 | 149 (FP64 basis), 61 | 62 (FP32)."""
+    edge = (61, 62) if f32 else (30, 31, 148, 149)
+    return ([(0, 5)] + [(n, k) for n in (1, 63, 64, 65) for k in (1, 2, 3, 4, 5)] + [(4099, k) for k in (1, 3) + edge + (255, 256)] +
+            [(65, 255), (65, 256), (131072, 2), (131073, 2), (16449, 2), (32769, 256) if f32 else (16385, 256)])
+
+
+def pass_c_shapes(f32):
+    """(n, k, mode): every k and every n with every destination mode the basis type has."""
+    shapes = [(n, k, (a * 5 + b) % (2 if f32 else 3)) for a, n in enumerate((1, 255, 256, 257, 4099)) for b, k in enumerate((1, 7, 8, 9, 256))]
+    return shapes + [(0, 7, 0), (524289, 3, 1 if f32 else 2)]
+
+
+def _pass_c_case(f32, i, n, k, mode):
+    return Case("pass_c_%s_n%d_k%d_%s" % (_ty(f32), n, k, PASS_MODES[mode]), "pass_c", n=n, k=k, mode=mode, f32=f32,
+                ld=n + (5 if mode == 2 else _pad(i)))
+
+
+def _mv_case(op, f32, n, nb, ks, tag=""):
+    return Case("%s_%s_n%d_nb%d%s" % (op, _ty(f32), n, nb, tag), op, n=n, nb=nb, ks=ks, f32=f32, ld=n + _pad(nb), mode=nb % 2 if op == "pass_c_mv" else 0)
+
+
+CASES += (
+    [Case("%s_%s_n%d_k%d" % (op, _ty(f32), n, k), op, n=n, k=k, f32=f32, ld=n + _pad(i))
+     for op in ("pass_a", "pass_b") for f32 in (False, True) for i, (n, k) in enumerate(tile_shapes(f32))] +
+    [_pass_c_case(f32, i, n, k, mode) for f32 in (False, True) for i, (n, k, mode) in enumerate(pass_c_shapes(f32))] +
+    [Case("%s_%s_n65_k%d" % (op, _ty(f32), k), op, n=65, k=k, f32=f32, ld=70, mode=0) for op in PASS_OPS for f32 in (False, True) for k in (0, 257)] +
+    [_mv_case(op, f32, n, nb, MV_KS[:nb]) for op in PASS_MV_OPS for f32 in (False, True) for n in (1, 65, 4099) for nb in (1, 2, 3, 4)] +
+    # one launch whose columns have own grids 256 / 258 / 256 / 258 (FP32: 512 / 514 / 512 / 514): the columns with the smaller
+    # grid take a second trip, and the last two workgroups of those columns leave before the barrier
+    [_mv_case(op, False, 16449, 4, (256, 1, 149, 31)) for op in ("pass_a_mv", "pass_b_mv")] +
+    [_mv_case(op, True, 32833, 4, (256, 1, 193, 2)) for op in ("pass_a_mv", "pass_b_mv")] +
+    [_mv_case(op, False, 65, nb, ks, tag) for op in PASS_MV_OPS
+     for nb, ks, tag in ((0, (), ""), (5, MV_KS, ""), (4, (5, 0, 3, 31), "_k0"), (4, (5, 3, 257, 31), "_k257"))] +
+    [Case("%s_n%d_m%d" % (op, n, m), op, n=n, m=m, ld=n + _pad(a + b)) for op in PROJ_OPS for a, n in enumerate(PROJ_N) for b, m in enumerate(PROJ_M)] +
+    [Case("%s_n524289_m9" % op, op, n=524289, m=9, ld=524289) for op in PROJ_OPS] +
+    # the chunk tails 3 to 6 (a kernel instance each), which the m above do not reach
+    [Case("%s_n257_m%d" % (op, m), op, n=257, m=m, ld=257 + _pad(m)) for op in PROJ_OPS for m in (3, 4, 5, 6)] +
+    [Case("%s_refused_n%d_m%d_ld%d" % (op, n, m, ld), op, n=n, m=m, ld=ld) for op in PROJ_OPS
+     for n, m, ld in ((257, 0, 257), (257, 33, 257), (0, 2, 0), (257, 2, 256))]
 )
 BY_NAME = {c.name: c for c in CASES}
 assert len(BY_NAME) == len(CASES)
@@ -869,6 +1397,86 @@ def restate_spmv(case, out, mutant=None):
         for k, (alpha, beta) in enumerate(SPMV_AB):
             y0 = np.full(nrows, np.nan) if beta == 0.0 else inp["y"][v]
             res["y%d" % k][v * ldy:v * ldy + nrows] = alpha * s + (beta * y0 if beta != 0.0 or mutant == "beta_nan" else 0.0)
+    return res
+
+
+def restate_pass(case, out, mutant=None):
+    """out of a single pass A, B or C with every defined output replaced by a float64 numpy restatement (sums in numpy's
+    order, the partials per workgroup as the grid strides).  Mutants:
+      pass A  "ragged"   drops the rows of the ragged last tile
+              "grid+1"   credits tile t to workgroup t mod (grid + 1) (what falls to the workgroup that does not exist goes to
+                         the last one): h1 stays right and agrees with the partials, only a partial against its own rows
+                         shows it
+              "w_float"  rounds w to float (a float-basis pass that narrows the vector as well)
+      pass B  "old_w"    h2 from the w before the update
+              "drop3"    the columns j = 3 mod 4 (the fourth quarter sum) missing from the update
+      pass C  "h1"       subtracts V h1 instead of V h2"""
+    which, batched, f32, n, ld, mode, ks, nb = orth_params(case)
+    assert not batched
+    inp, k, tab, grid = inputs(case), ks[0], out["tab"], int(out["grid"][0])
+    cols = strided_cols(inp["V0"], n, k, ld).astype(np.float64)
+    w, h1, h2 = inp["w0"], inp["h10"], inp["h20"]
+    res = {key: v.copy() for key, v in out.items()}
+
+    def put(key, kind, values, shift=0):
+        res[key][tab[kind, 0] + shift:tab[kind, 0] + shift + len(values)] = values
+
+    def tile_dots(wv):
+        t = cols * wv
+        if mutant == "ragged":
+            t[:, (n // TILE) * TILE:] = 0.0
+        if mutant == "grid+1":
+            wide = group_sums(t, TILE, grid + 1, np.float64)
+            part = wide[:, :grid].copy()
+            part[:, grid - 1] += wide[:, grid]
+        else:
+            part = group_sums(t, TILE, grid, np.float64)
+        return part.T.ravel(), part.sum(axis=1)            # part[b * k + j]
+
+    if which == "a":
+        part, h = tile_dots(w.astype(np.float32).astype(np.float64) if mutant == "w_float" else w)
+        put("P", 3, part)
+        put("H1", 4, h)
+    elif which == "b":
+        hh = h1.copy()
+        if mutant == "drop3":
+            hh[3::4] = 0.0
+        w_new = w - (cols * hh[:, None]).sum(axis=0)
+        part, h = tile_dots(w if mutant == "old_w" else w_new)
+        put("W", 1, w_new)
+        put("P", 3, part)
+        put("H2", 5, h)
+        put("O", 6, h1 + h)
+    else:
+        dst = w - (cols * (h1 if mutant == "h1" else h2)[:, None]).sum(axis=0)
+        part = group_sums((dst * dst)[None, :], 256, grid, np.float64)[0]
+        put(("DST", "W", "V")[mode], (2, 1, 0)[mode], dst, k * ld if mode == 2 else 0)
+        put("P", 3, part)
+        put("O", 6, np.array([np.sqrt(part.sum()), part.sum()]), k)
+    return res
+
+
+def restate_proj(case, out, mutant=None):
+    """out of proj_coeffs or border_product replaced by a float64 numpy restatement.  Mutants: "G_T" applies G transposed (the
+    border product: reads C row-major), "drop_chunk" leaves the columns of the last chunk out of the dots."""
+    inp, n, m, ld, F = inputs(case), case.p["n"], case.p["m"], case.p["ld"], case.family
+    grid = int(out["grid"][0])
+    Q, P, x = proj_cols(inp["Q"], n, m, ld), proj_cols(inp["P"], n, m, ld), inp["x"]
+    res = {key: v.copy() for key, v in out.items()}
+    for v in (0, 1):
+        G = inp["G"].reshape(m, m) if mutant == "G_T" else inp["G"].reshape(m, m).T
+        if F == "border_product":
+            z = inp["z"]
+            part = group_sums(P * z[:n], 256, grid, np.float64)
+            res["Y%d" % v][:n] = inp["y"] + (Q * z[n:, None]).sum(axis=0)
+            res["Y%d" % v][n:n + m] = part.sum(axis=1) + (G @ z[n:] if v else 0.0)
+        else:
+            part = group_sums(Q * x, 256, grid, np.float64)
+            if mutant == "drop_chunk":
+                part[((m - 1) // 8) * 8:] = 0.0
+            c = part.sum(axis=1)
+            res["H%d" % v][:m] = G @ c if v else c
+        res["P%d" % v][:grid * m] = part.T.ravel()
     return res
 
 
@@ -941,6 +1549,90 @@ def coverage(lib, cases):
                 tags.add("spmv_mv:repeated_column")
             if nrows % (256 // L):
                 tags.add("spmv_mv:partial_block")
+        elif F in PASS_OPS + PASS_MV_OPS:
+            tags |= orth_coverage(lib, c)
+        elif F in PROJ_OPS:
+            tags |= proj_coverage(lib, c)
+    return tags
+
+
+def orth_coverage(lib, case):
+    """The tags of one case of passes A, B, C or their batched forms, from the product's kry_tile_grid[_f32], kry_row_grid,
+    KRY_TILE, KRY_KMAX and KRY_LOCKSTEP_MAX."""
+    which, batched, f32, n, ld, mode, ks, nb = orth_params(case)
+    F, tags, T, huge = "%s_%s" % (case.family, _ty(f32)), set(), lib.tile, 1 << 40
+    add = lambda t: tags.add("%s:%s" % (F, t))
+    if batched and not 1 <= nb <= lib.lockstep_max:
+        add("nb=%d refused" % nb)
+        return tags
+    if any(k < 1 for k in ks) or any(k > lib.kmax for k in ks):
+        add("k=0 refused" if any(k < 1 for k in ks) else "k>kmax refused")
+        return tags
+    ntiles = -(-n // T)
+    grids = [lib.tile_grid(n, k, f32) if which in "ab" else lib.row_grid(n) for k in ks]
+    add("ld>n" if ld > n else "ld=n")
+    if batched:
+        add("nb=%d" % nb)
+        if len(set(grids)) > 1:
+            add("different_own_grids")
+        if any(g < max(grids) and ntiles > g for g in grids):
+            add("early_exit_and_second_trip")
+        if int(np.argmax(ks)) != 0:
+            add("largest_k_not_first")
+        tab = orth_layout(which, batched, n, ld, mode, ks, grids)[0]
+        for c in range(nb):
+            add("misaligned_column" if tab[1, c] % 2 else "aligned_column")
+        if which == "c":
+            add("mode=" + PASS_MODES[mode])
+        return tags
+    k, grid = ks[0], grids[0]
+    if which == "c":
+        add("n=0" if n == 0 else ("ragged" if n % 256 else "exact"))
+        add("k=%d" % k if k in (1, 7, 8, 9, lib.kmax) else "k=other")
+        add("mode=" + PASS_MODES[mode])
+        if n > 256:
+            add("more_workgroups")
+        if n > grid * 256:
+            add("second_trip")
+        if mode == 2 and ld > n:
+            add("basis_mode_with_padding")
+        return tags
+    cap = lib.tile_grid(huge, k, f32)                       # 256 x workgroups per CU
+    add("n=0" if n == 0 else ("one_ragged_tile" if ntiles == 1 and n % T else ("exact_tile_edge" if n % T == 0 else "ragged_last_tile")))
+    if ntiles == grid == cap:
+        add("full_grid_one_trip")
+    if ntiles > grid:
+        add("second_trip")
+        if n % T:
+            add("second_trip_ragged_last_tile")
+    add("wpc=%d" % (cap // 256))
+    if k < lib.kmax and lib.tile_grid(huge, k + 1, f32) < cap:
+        add("last_k_of_wpc=%d" % (cap // 256))
+    if k > 1 and lib.tile_grid(huge, k - 1, f32) > cap:
+        add("first_k_of_wpc=%d" % (cap // 256))
+    add("k=%d" % k if k in (1, 2, 3, 4, 5, lib.kmax - 1, lib.kmax) else "k=other")
+    add("stage2>256" if grid > 256 else "stage2<=256")
+    return tags
+
+
+def proj_coverage(lib, case):
+    """The tags of one projection or border case, from kry_row_grid and the product's chunk widths and limits."""
+    F, n, m, ld, tags = case.family, case.p["n"], case.p["m"], case.p["ld"], set()
+    add = lambda t: tags.add("%s:%s" % (F, t))
+    most, chunk = (lib.border_max, lib.border_chunk) if F == "border_product" else (lib.proj_max, lib.proj_chunk)
+    if proj_refused(case):
+        add("m=0 refused" if m < 1 else ("m>max refused" if m > most else ("n=0 refused" if n < 1 else "ld<n refused")))
+        return tags
+    add("m=%d" % m)
+    add("chunks=%d" % -(-m // chunk))
+    add("chunk_tail=%d" % (m % chunk or chunk))
+    add("n=1" if n == 1 else ("ragged" if n % 256 else "exact"))
+    add("ld>n" if ld > n else "ld=n")
+    if n > lib.row_grid(n) * 256:
+        add("second_trip")
+    if n > 256:
+        add("more_workgroups")
+    add("both_forms")         # every case runs without and with G (C of the border product), proj_update out of place and in place
     return tags
 
 
@@ -963,4 +1655,28 @@ REQUIRED = (
     # spmv_mv
     {"spmv_mv:L=1", "spmv_mv:L=2", "spmv_mv:L=4", "spmv_mv:L=8", "spmv_mv:group=2", "spmv_mv:group=3", "spmv_mv:group=4",
      "spmv_mv:trailing_single_column", "spmv_mv:ldx!=ldy", "spmv_mv:beta=0_over_nan", "spmv_mv:empty_row", "spmv_mv:long_row",
-     "spmv_mv:repeated_column", "spmv_mv:partial_block"})
+     "spmv_mv:repeated_column", "spmv_mv:partial_block"} |
+    # passes A and B, each basis type: the tile edges, the grid-stride trips, the workgroups-per-CU classes of the LDS tile
+    # (FP64: 8 up to k = 30, 7 from 31, 2 up to 148, 1 from 149; FP32: 8 up to 61, 7 from 62, 2 at 256), the k below and above
+    # the four quarter waves, both stage-two loops
+    {"%s_%s:%s" % (F, T, t) for F in ("pass_a", "pass_b") for T in ("f64", "f32") for t in (
+        "n=0", "one_ragged_tile", "exact_tile_edge", "ragged_last_tile", "full_grid_one_trip", "second_trip", "second_trip_ragged_last_tile",
+        "wpc=8", "wpc=7", "wpc=2", "last_k_of_wpc=8", "first_k_of_wpc=7", "k=1", "k=2", "k=3", "k=4", "k=5", "k=255", "k=256",
+        "stage2<=256", "stage2>256", "ld=n", "ld>n", "k=0 refused", "k>kmax refused")} |
+    {"%s_f64:%s" % (F, t) for F in ("pass_a", "pass_b") for t in ("wpc=1", "last_k_of_wpc=2", "first_k_of_wpc=1")} |
+    # pass C
+    {"pass_c_%s:%s" % (T, t) for T in ("f64", "f32") for t in (
+        "n=0", "ragged", "exact", "more_workgroups", "second_trip", "k=1", "k=7", "k=8", "k=9", "k=256", "mode=dst", "mode=w", "ld=n", "ld>n",
+        "k=0 refused", "k>kmax refused")} |
+    {"pass_c_f64:mode=basis", "pass_c_f64:basis_mode_with_padding"} |
+    # the batched passes
+    {"%s_%s:%s" % (F, T, t) for F in PASS_MV_OPS for T in ("f64", "f32") for t in (
+        "nb=1", "nb=2", "nb=3", "nb=4", "largest_k_not_first", "misaligned_column", "aligned_column", "ld=n", "ld>n")} |
+    {"%s_%s:%s" % (F, T, t) for F in ("pass_a_mv", "pass_b_mv") for T in ("f64", "f32") for t in ("different_own_grids", "early_exit_and_second_trip")} |
+    {"pass_c_mv_%s:mode=%s" % (T, t) for T in ("f64", "f32") for t in ("dst", "w")} |
+    {"%s_f64:%s" % (F, t) for F in PASS_MV_OPS for t in ("nb=0 refused", "nb=5 refused", "k=0 refused", "k>kmax refused")} |
+    # the projection and the border product
+    {"%s:%s" % (F, t) for F in PROJ_OPS for t in
+     ["m=%d" % m for m in PROJ_M] + ["chunk_tail=%d" % t for t in range(1, 9)] + ["chunks=%d" % c for c in (1, 2, 3, 4)] +
+     ["n=1", "ragged", "more_workgroups", "second_trip", "ld=n", "ld>n", "both_forms", "m=0 refused", "m>max refused", "n=0 refused",
+      "ld<n refused"]})

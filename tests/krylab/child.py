@@ -1,7 +1,8 @@
 """The run of every case of tests/krylab/cases.py in one process: through the product library (libkrylab_gpu.so) for
 tests/test_krylab_gpu.py, which starts it with a time limit, or through the simulator build.  Writes the whole output
 buffers of every case to <out>/<case>.npz and the coverage tags to <out>/coverage.txt.  The kernels read no environment
-switches, so one process serves all cases.
+switches, so one process serves all cases.  A batched case also runs the single launcher on every column's operands and
+stores whether the digests agree, so that both launches come from this one process.
 
 usage: python child.py OUT_DIR [sim]"""
 import importlib.util

@@ -1,5 +1,6 @@
-// kry_harness.cpp -- TEST-ONLY driver of the vector, reduction and update launchers of the native Krylov solver
-// (krylov.hpp) and of the multi-vector SpMV (device.hpp: spmv_mv), plain C++ without device code.
+// kry_harness.cpp -- TEST-ONLY driver of the launchers of the native Krylov solver (krylov.hpp: the vector, reduction and update
+// passes, the orthogonalisation passes A, B and C, the projection and the border product, and their batched forms) and of
+// the multi-vector SpMV (device.hpp: spmv_mv), plain C++ without device code.
 //
 // One extern "C" function per launcher: bind a context (kstream() is the bound context's stream), upload the arguments,
 // call exactly ONE launcher, dev::sync(), download, free.  The same source is linked twice (Makefile): against the
@@ -18,6 +19,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <exception>
 #include <memory>
 #include <string>
 #include <vector>
@@ -315,6 +317,188 @@ int krylab_spmv_mv(int32_t nrows, const int32_t* rowptr, const int32_t* col, con
   Out o(y, y_init * 8, y_words);
   dev::spmv_mv(nrows, d_rp, d_col, d_val, d_x, ldx, o.as<double>(), ldy, nv, alpha, beta, nnz_hint);
   dev::sync(); o.back();
+  KRYLAB_END
+}
+
+}  // extern "C"
+
+// ---- the orthogonalisation passes A, B, C, single and batched.  Operand kinds (rows of the offset table off[7][4], in
+// elements of the kind's type); every kind is ONE flat array and column c starts at off[kind * 4 + c]:
+//   0 V    the basis of column c: K[c] columns of n rows, leading dimension ld (float or double).  An input of exactly nV
+//          elements, or -- v_words > 0, double only -- an output buffer whose front is the caller's array: pass C with
+//          dst = column K[c] of the same basis (mode 2), the way the solver calls it
+//   1 W    the vector (output buffer with initial content: pass A must not write it)
+//   2 DST  pass C, mode 0: a separate destination (mode 1: dst = w)
+//   3 P    KryWork::part of column c      4 H1   KryWork::h1      5 H2   KryWork::h2      6 O   KryWork::out
+// P and O are output buffers that start as canary; H1 and H2 are output buffers whose front holds the caller's initial content
+// (h1 of pass B, h2 of pass C, and whatever the pass must leave alone).  A single-column entry takes column 0 of K and of the table.  When the launcher refuses, the
+// buffers still come back from the device before the error is returned: a refusal must have written nothing.
+namespace {
+
+enum { PASS_A, PASS_B, PASS_C };
+
+// sync and download whatever the launcher did, then pass its error on
+template <class Launch, class Back>
+void launch_and_fetch(Launch launch, Back back) {
+  std::exception_ptr ep;
+  try { launch(); } catch (...) { ep = std::current_exception(); }
+  dev::sync();
+  back();
+  if (ep) std::rethrow_exception(ep);
+}
+
+void run_pass(int which, bool batched, bool f32, int64_t n, int64_t ld, int32_t nb, int32_t mode, const int32_t* K, void* V, int64_t nV,
+              int64_t v_words, double* W, int64_t w_init, int64_t w_words, double* DST, int64_t dst_words, double* P,
+              int64_t p_words, double* H1, int64_t h1_init, int64_t h1_words, double* H2, int64_t h2_init, int64_t h2_words, double* O,
+              int64_t o_words, const int64_t* off) {
+  Freer f;
+  const size_t v_item = f32 ? 4 : 8;
+  if (mode == 2 && (f32 || v_words <= 0)) throw Error(-2, "krylab: dst inside the basis needs a double basis in an output buffer");
+  std::unique_ptr<Out> ov, odst;
+  const char* d_V = nullptr;
+  if (v_words > 0) { ov.reset(new Out(V, nV * 8, v_words)); d_V = ov->as<char>(); }
+  else d_V = (const char*)f(up((const char*)V, nV * (int64_t)v_item));
+  Out ow(W, w_init, w_words), op(P, 0, p_words), oh1(H1, h1_init, h1_words), oh2(H2, h2_init, h2_words), oo(O, 0, o_words);
+  if (DST) odst.reset(new Out(DST, 0, dst_words));
+  auto column = [&](int c, const void*& Vc, double*& wc, double*& dc, dev::KryWork& ws) {
+    Vc = d_V + (size_t)off[0 * 4 + c] * v_item;
+    wc = ow.as<double>() + off[1 * 4 + c];
+    dc = mode == 0 ? (odst ? odst->as<double>() + off[2 * 4 + c] : nullptr)
+       : mode == 1 ? wc : (double*)(d_V + (size_t)off[0 * 4 + c] * 8) + (int64_t)K[c] * ld;
+    ws.part = op.as<double>() + off[3 * 4 + c];
+    ws.h1 = oh1.as<double>() + off[4 * 4 + c];
+    ws.h2 = oh2.as<double>() + off[5 * 4 + c];
+    ws.out = oo.as<double>() + off[6 * 4 + c];
+  };
+  auto back = [&]() {
+    if (ov) ov->back();
+    if (odst) odst->back();
+    ow.back(); op.back(); oh1.back(); oh2.back(); oo.back();
+  };
+  if (!batched) {
+    const void* Vc; double *wc, *dc; dev::KryWork ws{};
+    column(0, Vc, wc, dc, ws);
+    const int32_t k = K[0];
+    launch_and_fetch([&]() {
+      if (f32) {
+        if (which == PASS_A) dev::kry_pass_a(n, k, (const float*)Vc, ld, wc, ws);
+        else if (which == PASS_B) dev::kry_pass_b(n, k, (const float*)Vc, ld, wc, ws);
+        else dev::kry_pass_c(n, k, (const float*)Vc, ld, wc, dc, ws);
+      } else {
+        if (which == PASS_A) dev::kry_pass_a(n, k, (const double*)Vc, ld, wc, ws);
+        else if (which == PASS_B) dev::kry_pass_b(n, k, (const double*)Vc, ld, wc, ws);
+        else dev::kry_pass_c(n, k, (const double*)Vc, ld, wc, dc, ws);
+      }
+    }, back);
+    return;
+  }
+  dev::KryBatch b{};
+  b.nb = nb;                                               // as given: the launcher must refuse 0 and 5
+  for (int c = 0; c < std::max(0, std::min<int>(nb, dev::KRY_LOCKSTEP_MAX)); c++) {
+    b.k[c] = K[c];
+    column(c, b.V[c], b.w[c], b.dst[c], b.ws[c]);
+  }
+  launch_and_fetch([&]() {
+    if (which == PASS_A) dev::kry_pass_a_mv(n, ld, b, f32);
+    else if (which == PASS_B) dev::kry_pass_b_mv(n, ld, b, f32);
+    else dev::kry_pass_c_mv(n, ld, b, f32);
+  }, back);
+}
+
+}  // namespace
+
+#define KRYLAB_PASS_ARGS                                                                                                         \
+  int32_t mode, const int32_t* K, void* V, int64_t nV, int64_t v_words, double* W, int64_t w_init, int64_t w_words, double* DST, \
+  int64_t dst_words, double* P, int64_t p_words, double* H1, int64_t h1_init, int64_t h1_words, double* H2,     \
+  int64_t h2_init, int64_t h2_words, double* O, int64_t o_words, const int64_t* off, char* err, int32_t errlen
+#define KRYLAB_PASS_PASS                                                                                                         \
+  mode, K, V, nV, v_words, W, w_init, w_words, DST, dst_words, P, p_words, H1, h1_init, h1_words, H2, h2_init, h2_words, \
+  O, o_words, off
+#define KRYLAB_PASS(name, id, f32)                                                          \
+  int krylab_##name(int64_t n, int64_t ld, KRYLAB_PASS_ARGS) {                              \
+    KRYLAB_TRY                                                                              \
+    run_pass(id, false, f32, n, ld, 1, KRYLAB_PASS_PASS);                                   \
+    KRYLAB_END                                                                              \
+  }
+#define KRYLAB_PASS_MV(name, id)                                                            \
+  int krylab_##name(int64_t n, int64_t ld, int32_t nb, int32_t f32, KRYLAB_PASS_ARGS) {     \
+    KRYLAB_TRY                                                                              \
+    run_pass(id, true, f32 != 0, n, ld, nb, KRYLAB_PASS_PASS);                              \
+    KRYLAB_END                                                                              \
+  }
+
+extern "C" {
+
+int32_t krylab_tile_grid(int64_t n, int32_t k) { return dev::kry_tile_grid(n, k); }
+int32_t krylab_tile_grid_f32(int64_t n, int32_t k) { return dev::kry_tile_grid_f32(n, k); }
+int32_t krylab_tile() { return dev::KRY_TILE; }
+int32_t krylab_proj_max() { return dev::KRY_PROJ_MAX; }
+int32_t krylab_proj_chunk() { return dev::KRY_PROJ_CHUNK; }
+int32_t krylab_border_max() { return dev::KRY_BORDER_MAX; }
+int32_t krylab_border_chunk() { return dev::KRY_BORDER_CHUNK; }
+
+KRYLAB_PASS(pass_a_f64, PASS_A, false)
+KRYLAB_PASS(pass_a_f32, PASS_A, true)
+KRYLAB_PASS(pass_b_f64, PASS_B, false)
+KRYLAB_PASS(pass_b_f32, PASS_B, true)
+KRYLAB_PASS(pass_c_f64, PASS_C, false)
+KRYLAB_PASS(pass_c_f32, PASS_C, true)
+KRYLAB_PASS_MV(pass_a_mv, PASS_A)
+KRYLAB_PASS_MV(pass_b_mv, PASS_B)
+KRYLAB_PASS_MV(pass_c_mv, PASS_C)
+
+// ---- projection vectors.  Q, P: exactly nQ, nP elements; G null: the identity.  ws.part and ws.h1 are output buffers (h1
+// with the caller's initial content: the coefficients of proj_update); x null: in place, y's initial content is x
+int krylab_proj_coeffs(int64_t n, int32_t m, const double* Q, int64_t nQ, int64_t ldq, const double* G, int64_t nG, const double* x,
+                       int64_t nx, double* P, int64_t p_words, double* H1, int64_t h1_init, int64_t h1_words, char* err, int32_t errlen) {
+  KRYLAB_TRY
+  Freer f;
+  const double* d_Q = f(up(Q, nQ)); const double* d_G = G ? f(up(G, nG)) : nullptr; const double* d_x = f(up(x, nx));
+  Out op(P, 0, p_words), oh(H1, h1_init, h1_words);
+  dev::KryWork ws{};
+  ws.part = op.as<double>(); ws.h1 = oh.as<double>();
+  launch_and_fetch([&]() { dev::kry_proj_coeffs(n, m, d_Q, ldq, d_G, d_x, ws); }, [&]() { op.back(); oh.back(); });
+  KRYLAB_END
+}
+int krylab_proj_update(int64_t n, int32_t m, const double* Pm, int64_t nP, int64_t ldp, const double* x, int64_t nx, double* Y, int64_t y_init,
+                       int64_t y_words, double* H1, int64_t h1_init, int64_t h1_words, char* err, int32_t errlen) {
+  KRYLAB_TRY
+  Freer f;
+  const double* d_P = f(up(Pm, nP)); const double* d_x = x ? f(up(x, nx)) : nullptr;
+  Out oy(Y, y_init, y_words), oh(H1, h1_init, h1_words);
+  dev::KryWork ws{};
+  ws.h1 = oh.as<double>();
+  launch_and_fetch([&]() { dev::kry_proj_update(n, m, d_P, ldp, d_x ? d_x : oy.as<double>(), oy.as<double>(), ws); },
+                   [&]() { oy.back(); oh.back(); });
+  KRYLAB_END
+}
+int krylab_oblique_project(int64_t n, int32_t m, const double* Q, int64_t nQ, int64_t ldq, const double* G, int64_t nG, const double* Pm,
+                           int64_t nP, int64_t ldp, const double* x, int64_t nx, double* Y, int64_t y_init, int64_t y_words, double* P,
+                           int64_t p_words, double* H1, int64_t h1_init, int64_t h1_words, char* err, int32_t errlen) {
+  KRYLAB_TRY
+  Freer f;
+  const double* d_Q = f(up(Q, nQ)); const double* d_G = G ? f(up(G, nG)) : nullptr; const double* d_P = f(up(Pm, nP));
+  const double* d_x = x ? f(up(x, nx)) : nullptr;
+  Out oy(Y, y_init, y_words), op(P, 0, p_words), oh(H1, h1_init, h1_words);
+  dev::KryWork ws{};
+  ws.part = op.as<double>(); ws.h1 = oh.as<double>();
+  launch_and_fetch([&]() { dev::kry_oblique_project(n, m, d_Q, ldq, d_G, d_P, ldp, d_x ? d_x : oy.as<double>(), oy.as<double>(), ws); },
+                   [&]() { oy.back(); op.back(); oh.back(); });
+  KRYLAB_END
+}
+// ---- the border product: z (n + m entries) is an output buffer too, so that the caller sees it unchanged; y is an output
+// buffer whose first n entries are K x
+int krylab_border_product(int64_t n, int32_t m, const double* V, int64_t nV, int64_t ldv, const double* W, int64_t nW, int64_t ldw,
+                          const double* C, int64_t nC, double* Z, int64_t z_init, int64_t z_words, double* Y, int64_t y_init, int64_t y_words, double* P,
+                          int64_t p_words, char* err, int32_t errlen) {
+  KRYLAB_TRY
+  Freer f;
+  const double* d_V = f(up(V, nV)); const double* d_W = f(up(W, nW)); const double* d_C = C ? f(up(C, nC)) : nullptr;
+  Out oz(Z, z_init, z_words), oy(Y, y_init, y_words), op(P, 0, p_words);
+  dev::KryWork ws{};
+  ws.part = op.as<double>();
+  launch_and_fetch([&]() { dev::kry_border_product(n, m, d_V, ldv, d_W, ldw, d_C, oz.as<double>(), oy.as<double>(), ws); },
+                   [&]() { oz.back(); oy.back(); op.back(); });
   KRYLAB_END
 }
 

@@ -14,24 +14,30 @@ namespace dev {
 
 namespace {
 void check_batch(int nb) { if (nb < 1 || nb > KRY_LOCKSTEP_MAX) throw Error(-2, "batched launch: 1 <= columns <= 4"); }
+// as check_batch of krylov_hip.hip: every k is checked before the first column runs, so a refused launch writes nothing
+void check_batch(const KryBatch& b) {
+  check_batch(b.nb);
+  for (int c = 0; c < b.nb; c++)
+    if (b.k[c] < 1 || b.k[c] > KRY_KMAX) throw Error(-2, "orthogonalisation: 1 <= k <= 256 columns");
+}
 }  // namespace
 
 void kry_pass_a_mv(int64_t n, int64_t ldv, const KryBatch& b, bool f32) {
-  check_batch(b.nb);
+  check_batch(b);
   for (int c = 0; c < b.nb; c++) {
     if (f32) kry_pass_a(n, b.k[c], (const float*)b.V[c], ldv, b.w[c], b.ws[c]);
     else kry_pass_a(n, b.k[c], (const double*)b.V[c], ldv, b.w[c], b.ws[c]);
   }
 }
 void kry_pass_b_mv(int64_t n, int64_t ldv, const KryBatch& b, bool f32) {
-  check_batch(b.nb);
+  check_batch(b);
   for (int c = 0; c < b.nb; c++) {
     if (f32) kry_pass_b(n, b.k[c], (const float*)b.V[c], ldv, b.w[c], b.ws[c]);
     else kry_pass_b(n, b.k[c], (const double*)b.V[c], ldv, b.w[c], b.ws[c]);
   }
 }
 void kry_pass_c_mv(int64_t n, int64_t ldv, const KryBatch& b, bool f32) {
-  check_batch(b.nb);
+  check_batch(b);
   for (int c = 0; c < b.nb; c++) {
     if (f32) kry_pass_c(n, b.k[c], (const float*)b.V[c], ldv, b.w[c], b.dst[c], b.ws[c]);
     else kry_pass_c(n, b.k[c], (const double*)b.V[c], ldv, b.w[c], b.dst[c], b.ws[c]);

@@ -1,5 +1,6 @@
-"""-m "not gpu": the vector, reduction and update launchers of the native Krylov solver, their batched forms and spmv_mv one
-by one (tests/krylab) on the test-only simulators, against the numpy references of the lab.  On the simulator a batched
+"""-m "not gpu": the vector, reduction and update launchers of the native Krylov solver, the orthogonalisation passes A, B
+and C pass by pass, the projection and border-product launchers, their batched forms and spmv_mv one by one (tests/krylab)
+on the test-only simulators, against the numpy references of the lab.  On the simulator a batched
 launcher is a loop over the single one, so this run proves the harness, the references, the canaries, the bounds and the
 coverage bookkeeping on a machine without a GPU, and that every check bites (perturbations, numpy mutants, stray writes);
 tests/test_krylab_gpu.py runs the same cases through the product library and pins the kernels."""
@@ -52,6 +53,7 @@ def test_case_matches_reference(sim, case):
     fails, ratio = kl.check_case(case, result(sim, case))
     print("krylab sim: %-34s error / bound %.3g" % (case.name, ratio))
     assert fails == []
+    assert all(u == 0 for u in kl.SQRT_ULPS.values())    # out[k] of pass C: the host's sqrt is numpy's, bit for bit
 
 
 def test_case_list_covers_every_branch(sim):
@@ -61,7 +63,9 @@ def test_case_list_covers_every_branch(sim):
 def test_coverage_notices_a_missing_case(sim):
     """The coverage check itself: each of these cases is the only one that reaches its branch."""
     for names, tag in ((["dot_524288"], "dot:full_grid_one_trip"), (["update_f64_n257_k0", "update_f32_n257_k0"], "update:k=0"),
-                       (["cg_xr_mv_n257_nb5"], "cg_xr_mv:nb=5 refused")):
+                       (["cg_xr_mv_n257_nb5"], "cg_xr_mv:nb=5 refused"), (["pass_b_f32_n131072_k2"], "pass_b_f32:full_grid_one_trip"),
+                       (["pass_c_f64_n524289_k3_basis"], "pass_c_f64:second_trip"), (["pass_c_mv_f64_n65_nb4_k0"], "pass_c_mv_f64:k=0 refused"),
+                       (["proj_coeffs_n524289_m9"], "proj_coeffs:second_trip"), (["border_product_n257_m5"], "border_product:chunk_tail=5")):
         got = kl.coverage(sim, [c for c in kl.CASES if c.name not in names])
         assert kl.REQUIRED - got == {tag}
     got = kl.coverage(sim, [c for c in kl.CASES if not (c.family == "spmv_mv" and c.p["nv"] in (2, 6))])
@@ -75,7 +79,18 @@ SHARP = [("dot_257", "out", 0), ("dot_65537", "out", 0), ("cg_xr_257", "x1", 200
          ("cg_p_257", "p0", 256), ("cg_p_65537", "p1", 65536), ("update_f64_n257_k9_ld5", "x", 256), ("update_f32_n4099_k256_ld0", "x", 4098),
          ("dot_mv_n257_nb3", "O", 2 * kl.MV_OUT_STRIDE), ("cg_xr_mv_n257_nb4", "Y", None), ("cg_xr_mv_n257_nb4", "R", None),
          ("cg_xr_mv_n257_nb4", "O", 3 * kl.MV_OUT_STRIDE), ("cg_p_mv_n65537_nb2", "Y", None), ("spmv_mv_65_L4_nv7", "y2", None),
-         ("spmv_mv_257_L1_nv6", "y0", None)]
+         ("spmv_mv_257_L1_nv6", "y0", None),
+         # a coefficient, a partial (the one of the ragged last tile), a row of w / dst, the squared norm, a d_j, a row of y
+         ("pass_a_f64_n4099_k255", "H1", 254), ("pass_a_f64_n4099_k255", "P", 64 * 255 + 254), ("pass_a_f32_n4099_k62", "H1", 61),
+         ("pass_a_f32_n65_k256", "P", 256 + 255), ("pass_b_f64_n4099_k149", "W", 4098), ("pass_b_f64_n4099_k149", "H2", 148),
+         ("pass_b_f64_n65_k3", "P", 3 + 2), ("pass_b_f32_n4099_k61", "W", 0), ("pass_c_f64_n4099_k256_dst", "DST", 4098),
+         ("pass_c_f64_n4099_k8_w", "W", 4098), ("pass_c_f64_n4099_k9_basis", "V", None), ("pass_c_f64_n4099_k256_dst", "O", 257),
+         ("pass_c_f32_n4099_k256_dst", "P", 16), ("pass_a_mv_f64_n4099_nb4", "H1", None), ("pass_a_mv_f32_n65_nb2", "P", None),
+         ("pass_b_mv_f32_n65_nb3", "W", None), ("pass_b_mv_f64_n4099_nb2", "P", None), ("pass_b_mv_f64_n4099_nb2", "H2", None),
+         ("pass_c_mv_f64_n4099_nb2", "DST", None), ("pass_c_mv_f32_n65_nb3", "O", None), ("proj_coeffs_n257_m32", "H1", 31),
+         ("proj_coeffs_n4099_m9", "H0", 8), ("proj_coeffs_n4099_m9", "P1", None), ("proj_update_n257_m7", "Y0", 256),
+         ("proj_update_n4099_m32", "Y1", 0), ("oblique_project_n257_m17", "Y1", 256), ("oblique_project_n257_m8", "H0", 7),
+         ("border_product_n4099_m9", "Y1", 4099 + 8), ("border_product_n4099_m9", "Y0", 100), ("border_product_n257_m32", "P1", None)]
 
 
 def last_written(buf):
@@ -198,6 +213,91 @@ def test_spmv_mv_check_catches_a_mutant(sim, mutant, names):
         res = result(sim, case)
         assert reference_fails(case, kl.restate_spmv(case, res)) == [], name
         assert reference_fails(case, kl.restate_spmv(case, res, mutant)), (mutant, name)
+
+
+# ---- the orthogonalisation passes, the projection and the border product
+def test_pass_b_sum_check_catches_a_flipped_bit(sim):
+    """out[j] = h1[j] + h2[j] is one add: the lowest mantissa bit of one entry fails.  So do two ulps in the norm of pass C."""
+    for name, pos in (("pass_b_f64_n4099_k149", 148), ("pass_b_f32_n65_k4", 0), ("pass_b_mv_f32_n65_nb3", None)):
+        case = kl.BY_NAME[name]
+        res = result(sim, case)
+        assert kl.check_case(case, res)[0] == []
+        bad = copy_of(res)
+        bad["O"].view(np.uint64)[last_written(bad["O"]) if pos is None else pos] ^= np.uint64(1)
+        fails = kl.check_case(case, bad)[0]
+        assert any("out = h1 + h2 differs from the restatement" in f for f in fails), fails
+    case = kl.BY_NAME["pass_c_f64_n4099_k8_w"]
+    bad = copy_of(result(sim, case))
+    bad["O"].view(np.uint64)[8] += np.uint64(2)
+    assert any("ulps from the restatement" in f for f in kl.check_case(case, bad)[0])
+
+
+def fails_of_restatement(sim, name, restate, mutant):
+    case = kl.BY_NAME[name]
+    res = result(sim, case)
+    assert kl.check_case(case, restate(case, res))[0] == [], name
+    fails = reference_fails(case, restate(case, res, mutant))
+    assert fails, (mutant, name)
+    return fails
+
+
+@pytest.mark.parametrize("mutant,names", [
+    ("ragged", ["pass_a_f64_n1_k1", "pass_a_f64_n65_k3", "pass_a_f64_n4099_k255", "pass_a_f32_n63_k5", "pass_a_f32_n4099_k256",
+                "pass_a_f64_n131073_k2"]),
+    ("grid+1", ["pass_a_f64_n131073_k2", "pass_a_f32_n131073_k2", "pass_a_f64_n16385_k256"]),
+    ("w_float", ["pass_a_f32_n65_k2", "pass_a_f32_n4099_k62", "pass_a_f32_n4099_k256"]),
+    ("old_w", ["pass_b_f64_n1_k1", "pass_b_f64_n65_k5", "pass_b_f64_n4099_k149", "pass_b_f32_n4099_k61"]),
+    ("drop3", ["pass_b_f64_n64_k4", "pass_b_f64_n65_k5", "pass_b_f64_n4099_k256", "pass_b_f32_n65_k255"]),
+    ("h1", ["pass_c_f64_n1_k1_dst", "pass_c_f64_n4099_k9_basis", "pass_c_f64_n4099_k8_w", "pass_c_f32_n4099_k256_dst", "pass_c_f32_n257_k8_w"])])
+def test_pass_check_catches_a_mutant(sim, mutant, names):
+    """Pass A without the ragged last tile, with the tiles credited to the wrong workgroup, with w rounded to float; pass B
+    with h2 from the old w, without the fourth quarter sum; pass C with h1."""
+    for name in names:
+        fails = fails_of_restatement(sim, name, kl.restate_pass, mutant)
+        if mutant == "grid+1":                           # the coefficient and stage two are right: only the partials show it
+            assert all("a partial against its rows" in f for f in fails), fails
+
+
+@pytest.mark.parametrize("mutant,names", [
+    ("G_T", ["proj_coeffs_n1_m2", "proj_coeffs_n257_m9", "proj_coeffs_n4099_m32", "border_product_n1_m2", "border_product_n257_m9",
+             "border_product_n4099_m32"]),
+    ("drop_chunk", ["proj_coeffs_n1_m1", "proj_coeffs_n257_m9", "proj_coeffs_n4099_m17", "proj_coeffs_n257_m32", "proj_coeffs_n257_m5"])])
+def test_projection_check_catches_a_mutant(sim, mutant, names):
+    """G applied transposed (the border tail: C read row-major); the dots without the last chunk of columns."""
+    for name in names:
+        fails_of_restatement(sim, name, kl.restate_proj, mutant)
+
+
+def test_pass_canaries_notice_a_stray_write(sim):
+    """A partial too many, out[k] after pass B, h2[0] after pass A, the padding behind column k - 1 of a basis that takes dst,
+    the scratch of a batched column behind its own grid, and w after pass A."""
+    def stray(name, key, pos, value=0.0):
+        case = kl.BY_NAME[name]
+        res = result(sim, case)
+        assert kl.check_case(case, res)[0] == []
+        bad = copy_of(res)
+        assert bad[key].view(np.uint64)[pos] != np.float64(value).view(np.uint64)
+        bad[key][pos] = value
+        fails = kl.check_case(case, bad)[0]
+        assert any("written outside its output set" in f for f in fails), (name, key, fails)
+        return res
+    res = stray("pass_a_f64_n65_k3", "P", 2 * 3)
+    assert int((res["P"].view(np.uint64) != np.uint64(kl.CANARY)).sum()) == 2 * 3          # exactly grid * k partials
+    stray("pass_b_f64_n65_k3", "O", 3)
+    stray("pass_a_f64_n65_k3", "H2", 0)
+    stray("pass_a_f32_n4099_k62", "W", 4098)
+    case = kl.BY_NAME["pass_c_f64_n255_k9_basis"]
+    assert case.p["ld"] == 260
+    stray(case.name, "V", 8 * 260 + 255)
+    stray(case.name, "H1", 0)
+    case = kl.BY_NAME["pass_a_mv_f64_n65_nb3"]
+    res = result(sim, case)
+    stray(case.name, "P", int(res["tab"][3, 1]) + int(res["grid"][1]) * case.p["ks"][1])
+    stray("proj_coeffs_n257_m9", "H0", 9)
+    stray("proj_coeffs_n257_m9", "P1", 2 * 9)
+    stray("proj_update_n257_m7", "H1", 0)
+    stray("border_product_n257_m9", "Z1", 257)
+    stray("border_product_n257_m9", "Y1", 257 + 9)
 
 
 # ---- canaries

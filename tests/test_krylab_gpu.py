@@ -1,8 +1,10 @@
-"""-m gpu: the vector, reduction and update kernels of the native Krylov solver, their batched (lock-step) forms and
-k_spmv_mv one by one on the MI355X (tests/krylab through the product library), against the numpy references of the lab.
+"""-m gpu: the vector, reduction and update kernels of the native Krylov solver, the orthogonalisation passes A, B and C pass
+by pass (both basis types), the projection and border-product kernels, their batched (lock-step) forms and k_spmv_mv one
+by one on the MI355X (tests/krylab through the product library), against the numpy references of the lab.
 The simulator run (tests/test_krylab.py) proves the harness, the references and the bounds; this run pins the kernels:
-every case within its bound or bit-exact, every batched column bit for bit the single launch, every spmv_mv column bit for
-bit spmv(), nothing written outside the output set.
+every case within its bound or bit-exact, every partial of a tiled pass against its own rows, every batched column bit for
+bit the single launch, every spmv_mv column bit for bit spmv(), nothing written outside the output set (the scratch of a
+batched column is as long as that column's own grid needs), a refused launch writes nothing.
 
 One child process (tests/krylab/child.py) runs every case, with a time limit; after a child that failed, timed out or died
 from a signal nothing more is started on the GPU, and every test reports that child."""
@@ -68,6 +70,9 @@ def test_kernels_match_reference(run):
         worst[case.family] = max(worst.get(case.family, 0.0), ratio)
     for fam in sorted(worst):
         print("krylab gpu: %-18s largest error / bound %.3g" % (fam, worst[fam]))
+    ulps = kl.SQRT_ULPS.values()
+    print("krylab gpu: out[k] of pass C against sqrt(out[k + 1]) of numpy: %d norms, %d bit-equal, largest distance %d ulp"
+          % (len(ulps), sum(u == 0 for u in ulps), max(ulps, default=0)))
     assert bad == []
 
 
