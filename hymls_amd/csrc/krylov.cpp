@@ -99,6 +99,15 @@ struct hymls_mi_solver {
 
 namespace {
 
+// device scratch of one call, freed when the call ends, by return or by exception
+struct Scratch {
+  double* p;
+  explicit Scratch(size_t doubles) : p((double*)dev::alloc(doubles * sizeof(double))) {}
+  ~Scratch() { dev::free(p); }
+  Scratch(const Scratch&) = delete;
+  Scratch& operator=(const Scratch&) = delete;
+};
+
 struct Run {
   hymls_mi_solver* s;
   LevelSolver* L;
@@ -122,6 +131,16 @@ struct Run {
   dev::KryWork pws{};
 
   void mark(int phase, bool begin) { if (s->profiling) dev::kry_mark(s->timer, phase, begin); }
+  // the seven vectors of a column, in one block of 7 ld doubles
+  void bind_vectors(double* v) {
+    x = v; r = v + ld; w = v + 2 * ld; t = v + 3 * ld; p = v + 4 * ld; prev = v + 5 * ld; bst = v + 6 * ld;
+  }
+  // x <- the start vector of a column: random values (rnd), the solution stored by the solve before it, or zero
+  void start_vector(const std::vector<double>& rnd, const double* previous) {
+    if (s->p.initial_vector == 1) dev::h2d(x, rnd.data(), n * sizeof(double));
+    else if (s->p.initial_vector == 2 && s->have_prev) dev::d2d(x, previous, n * sizeof(double));
+    else dev::zero(x, n * sizeof(double));
+  }
   // the two hooks of the iteration; with a border: M^{-1} [in; T] = [out; S] with T and S in the tails, and
   // [K V; W' C] in = K in(0:nh) followed by the border product
   void prec(const double* in, double* out) {
@@ -361,21 +380,26 @@ struct Run {
   }
 #endif
 
-  // preconditioned CG (solver.py: Solver._cg)
-  void cg(const double* b, int& its, double& rel) {
-    const hymls_mi_solver_params& P = s->p;
-    double* z = w;
-    double* q = t;
+  // the start of CG: r = b - K x (b itself where x = 0), z = M^{-1} r in w, p = z;  rz = r . z, r0 = ||r||
+  void cg_begin(const double* b, double& rz, double& r0) {
     if (dot(x, x) > 0.0) {
       matvec(x, t);
       mark(3, true); dev::kry_sub(n, b, t, r); mark(3, false);
     } else {
       dev::d2d(r, b, n * sizeof(double));
     }
-    prec(r, z);
-    dev::d2d(p, z, n * sizeof(double));
-    double rz = dot(r, z);
-    const double r0 = norm(r);
+    prec(r, w);
+    dev::d2d(p, w, n * sizeof(double));
+    rz = dot(r, w);
+    r0 = norm(r);
+  }
+  // preconditioned CG (solver.py: Solver._cg)
+  void cg(const double* b, int& its, double& rel) {
+    const hymls_mi_solver_params& P = s->p;
+    double* z = w;
+    double* q = t;
+    double rz = 0, r0 = 0;
+    cg_begin(b, rz, r0);
     its = 0;
     rel = 1.0;
     if (r0 == 0.0) { rel = 0.0; return; }
@@ -541,23 +565,13 @@ struct Lockstep {
     for (int c = 0; c < nc; c++) { its[c] = A[c].its; rel[c] = A[c].rel; }
   }
 
-  // preconditioned CG: the start of Run::cg column by column, then its loop with the active columns side by side
+  // preconditioned CG: Run::cg_begin column by column, then the loop of Run::cg with the active columns side by side
   void cg() {
     const hymls_mi_solver_params& P = s->p;
     host.assign((size_t)LK_MAX * LK_OUT, 0.0);
     double rz[LK_MAX], r0[LK_MAX];
     for (int c = 0; c < nc; c++) {
-      Run& r = R[c];
-      if (r.dot(r.x, r.x) > 0.0) {
-        r.matvec(r.x, r.t);
-        mark(3, true); dev::kry_sub(n, b[c], r.t, r.r); mark(3, false);
-      } else {
-        dev::d2d(r.r, b[c], n * sizeof(double));
-      }
-      r.prec(r.r, r.w);
-      dev::d2d(r.p, r.w, n * sizeof(double));
-      rz[c] = r.dot(r.r, r.w);
-      r0[c] = r.norm(r.r);
+      R[c].cg_begin(b[c], rz[c], r0[c]);
       its[c] = 0;
       rel[c] = 1.0;
       active[c] = true;
@@ -794,10 +808,7 @@ int solve_columns(hymls_mi_solver* s, const HandleView& hv_, int bm, const doubl
     s->ld = std::max<int64_t>(16, (n + 15) / 16 * 16);
     s->vec = (double*)dev::alloc((size_t)7 * s->ld * sizeof(double));
     s->work = (double*)dev::alloc(dev::kry_work_doubles() * sizeof(double));
-    s->ws.part = s->work;
-    s->ws.h1 = s->ws.part + (size_t)dev::KRY_MAXGRID * dev::KRY_KMAX;
-    s->ws.h2 = s->ws.h1 + dev::KRY_KMAX;
-    s->ws.out = s->ws.h2 + dev::KRY_KMAX;
+    s->ws = dev::kry_work_at(s->work);
   }
   if (gm && (m > s->m_alloc || s->basis_bits != s->bits_alloc)) {
     dev::sync();
@@ -824,9 +835,7 @@ int solve_columns(hymls_mi_solver* s, const HandleView& hv_, int bm, const doubl
   if (s->pm > 0) ready_projection(s, hv_, R);   // (a bordered solve with projection vectors has been refused before)
 #endif
   s->cols.clear();
-  double* v = s->vec;
-  R.x = v; R.r = v + s->ld; R.w = v + 2 * s->ld; R.t = v + 3 * s->ld; R.p = v + 4 * s->ld;
-  R.prev = v + 5 * s->ld; R.bst = v + 6 * s->ld;
+  R.bind_vectors(s->vec);
   std::vector<double> rnd;
   if (s->p.initial_vector == 1) {
     const ivec& gids = L->owned_gids();
@@ -849,23 +858,17 @@ int solve_columns(hymls_mi_solver* s, const HandleView& hv_, int bm, const doubl
       for (int c = 0; c < G.nc; c++) {
         Run& Rc = G.R[c];
         Rc = R;
-        double* vc = c == 0 ? s->vec : s->lk_vec[c];
-        Rc.x = vc; Rc.r = vc + s->ld; Rc.w = vc + 2 * s->ld; Rc.t = vc + 3 * s->ld; Rc.p = vc + 4 * s->ld;
-        Rc.prev = vc + 5 * s->ld; Rc.bst = vc + 6 * s->ld;
         if (c > 0) {
+          Rc.bind_vectors(s->lk_vec[c]);
           Rc.Vb = s->lk_V[c];
-          Rc.ws.part = s->lk_work[c];
-          Rc.ws.h1 = Rc.ws.part + (size_t)dev::KRY_MAXGRID * dev::KRY_KMAX;
-          Rc.ws.h2 = Rc.ws.h1 + dev::KRY_KMAX;
+          Rc.ws = dev::kry_work_at(s->lk_work[c]);
         }
         Rc.ws.out = s->lk_out + c * LK_OUT;   // the out areas of a group: one block, one copy per step
         const double* b = B + (int64_t)(c0 + c) * ldb;
         if (!on_device) { dev::h2d(Rc.bst, b, n * sizeof(double)); b = Rc.bst; }
         G.b[c] = b;
         // "Previous": every column of the group starts from the solution stored before the group
-        if (s->p.initial_vector == 1) dev::h2d(Rc.x, rnd.data(), n * sizeof(double));
-        else if (s->p.initial_vector == 2 && s->have_prev) dev::d2d(Rc.x, R.prev, n * sizeof(double));
-        else dev::zero(Rc.x, n * sizeof(double));
+        Rc.start_vector(rnd, R.prev);
       }
       R.mark(0, true);
       if (!gm) G.cg();
@@ -899,9 +902,7 @@ int solve_columns(hymls_mi_solver* s, const HandleView& hv_, int bm, const doubl
       else dev::zero(R.bst + nh, bm * sizeof(double));
       b = R.bst;
     } else if (!on_device) { dev::h2d(R.bst, b, n * sizeof(double)); b = R.bst; }
-    if (s->p.initial_vector == 1) dev::h2d(R.x, rnd.data(), n * sizeof(double));
-    else if (s->p.initial_vector == 2 && s->have_prev) dev::d2d(R.x, R.prev, n * sizeof(double));
-    else dev::zero(R.x, n * sizeof(double));
+    R.start_vector(rnd, R.prev);
     R.mark(0, true);
 #ifdef HYMLS_MI_PROJECTED_SOLVER
     // the start vector in the complement: x0 <- x0 - BV (V' x0) (reference BaseSolver.cpp:339-345)
@@ -946,6 +947,28 @@ int solve_columns(hymls_mi_solver* s, const HandleView& hv_, int bm, const doubl
     s->err = buf;
   }
   return status;
+}
+
+// one ICGS(2) step on caller-owned device arrays (hymls_mi_orthogonalize, _f32): w in place, the coefficients and the norm
+// to the host; vnext (FP32 basis only, may be null): the rounded new column (float)(w / ||w||)
+template <class BT>
+void orthogonalize_one(const HandleView& hv, const char* name, int64_t n, int32_t k, const BT* V, int64_t ldv, double* w,
+                       float* vnext, double* hcoef, double* wnorm) {
+  dev::bind(hv.ctx);
+  HYMLS_CHECK(n >= 1 && k >= 1 && k <= dev::KRY_KMAX && ldv >= n && V && w && hcoef && wnorm, -2,
+              std::string(name) + ": need n >= 1, 1 <= k <= 256, ldv >= n and non-null arrays");
+  Scratch work(dev::kry_work_doubles());
+  const dev::KryWork ws = dev::kry_work_at(work.p);
+  std::vector<double> hk(k + 1);
+  const bool dist = hv.comm->distributed();
+  Run::orthogonalize_step(ws, hv.comm, dist, n, k, V, ldv, w, w, hk.data());
+  if constexpr (sizeof(BT) == 4) {
+    if (vnext) dev::kry_round_scale_by(n, w, ws.out + k, vnext);
+  }
+  if (!dist) dev::d2h(hk.data(), ws.out, (k + 1) * sizeof(double));
+  else dev::sync();   // (the rounding store has ended before the scratch is freed)
+  std::copy(hk.begin(), hk.begin() + k, hcoef);
+  *wnorm = hk[k];
 }
 }  // namespace
 
@@ -1039,24 +1062,7 @@ int hymls_mi_orthogonalize(hymls_mi_t* h, int64_t n, int32_t k, const double* V,
   if (!h) return -2;
   HandleView hv = handle_view(h);
   try {
-    dev::bind(hv.ctx);
-    HYMLS_CHECK(n >= 1 && k >= 1 && k <= dev::KRY_KMAX && ldv >= n && V && w && hcoef && wnorm, -2,
-                "orthogonalize: need n >= 1, 1 <= k <= 256, ldv >= n and non-null arrays");
-    double* work = (double*)dev::alloc(dev::kry_work_doubles() * sizeof(double));
-    dev::KryWork ws;
-    ws.part = work;
-    ws.h1 = work + (size_t)dev::KRY_MAXGRID * dev::KRY_KMAX;
-    ws.h2 = ws.h1 + dev::KRY_KMAX;
-    ws.out = ws.h2 + dev::KRY_KMAX;
-    std::vector<double> hk(k + 1);
-    const bool dist = hv.comm->distributed();
-    try {
-      Run::orthogonalize_step(ws, hv.comm, dist, n, k, V, ldv, w, w, hk.data());
-      if (!dist) dev::d2h(hk.data(), ws.out, (k + 1) * sizeof(double));
-    } catch (...) { dev::free(work); throw; }
-    dev::free(work);
-    std::copy(hk.begin(), hk.begin() + k, hcoef);
-    *wnorm = hk[k];
+    orthogonalize_one(hv, "orthogonalize", n, k, V, ldv, w, nullptr, hcoef, wnorm);
   } catch (const hymls::Error& e) { *hv.err = e.what(); return e.code; }
   catch (const std::exception& e) { *hv.err = e.what(); return -3; }
   return 0;
@@ -1071,26 +1077,7 @@ int hymls_mi_orthogonalize_f32(hymls_mi_t* h, int64_t n, int32_t k, const float*
     (void)n; (void)k; (void)V; (void)ldv; (void)w; (void)vnext; (void)hcoef; (void)wnorm;
     throw hymls::Error(-99, "this build has no FP32 basis kernels (the test-only simulator without them)");
 #else
-    dev::bind(hv.ctx);
-    HYMLS_CHECK(n >= 1 && k >= 1 && k <= dev::KRY_KMAX && ldv >= n && V && w && hcoef && wnorm, -2,
-                "orthogonalize_f32: need n >= 1, 1 <= k <= 256, ldv >= n and non-null arrays");
-    double* work = (double*)dev::alloc(dev::kry_work_doubles() * sizeof(double));
-    dev::KryWork ws;
-    ws.part = work;
-    ws.h1 = work + (size_t)dev::KRY_MAXGRID * dev::KRY_KMAX;
-    ws.h2 = ws.h1 + dev::KRY_KMAX;
-    ws.out = ws.h2 + dev::KRY_KMAX;
-    std::vector<double> hk(k + 1);
-    const bool dist = hv.comm->distributed();
-    try {
-      Run::orthogonalize_step(ws, hv.comm, dist, n, k, V, ldv, w, w, hk.data());
-      if (vnext) dev::kry_round_scale_by(n, w, ws.out + k, vnext);
-      if (!dist) dev::d2h(hk.data(), ws.out, (k + 1) * sizeof(double));
-      else dev::sync();
-    } catch (...) { dev::free(work); throw; }
-    dev::free(work);
-    std::copy(hk.begin(), hk.begin() + k, hcoef);
-    *wnorm = hk[k];
+    orthogonalize_one(hv, "orthogonalize_f32", n, k, V, ldv, w, vnext, hcoef, wnorm);
 #endif
   } catch (const hymls::Error& e) { *hv.err = e.what(); return e.code; }
   catch (const std::exception& e) { *hv.err = e.what(); return -3; }
@@ -1110,16 +1097,13 @@ int hymls_mi_border_product(hymls_mi_t* h, int64_t n, int32_t m, const double* V
     HYMLS_CHECK(n >= 1 && m >= 1 && m <= HYMLS_MI_SOLVER_MAX_BORDER && ldv >= n && ldw >= n && V && W && z && y && z != y, -2,
                 "border_product: need n >= 1, 1 <= m <= 32, ldv and ldw >= n and non-null, distinct arrays");
     const int nb = dev::kry_row_grid(n);
-    double* work = (double*)dev::alloc(((size_t)nb * m + (size_t)m * m) * sizeof(double));
+    Scratch work((size_t)nb * m + (size_t)m * m);
     dev::KryWork ws{};
-    ws.part = work;
+    ws.part = work.p;
     double* dC = nullptr;
-    try {
-      if (C) { dC = work + (size_t)nb * m; dev::h2d(dC, C, (size_t)m * m * sizeof(double)); }
-      dev::kry_border_product(n, m, V, ldv, W, ldw, dC, z, y, ws);
-      dev::sync();
-    } catch (...) { dev::free(work); throw; }
-    dev::free(work);
+    if (C) { dC = work.p + (size_t)nb * m; dev::h2d(dC, C, (size_t)m * m * sizeof(double)); }
+    dev::kry_border_product(n, m, V, ldv, W, ldw, dC, z, y, ws);
+    dev::sync();
 #endif
   } catch (const hymls::Error& e) { *hv.err = e.what(); return e.code; }
   catch (const std::exception& e) { *hv.err = e.what(); return -3; }
@@ -1237,16 +1221,14 @@ int hymls_mi_solver_apply_projected(hymls_mi_solver_t* s, int which, const doubl
   const int64_t n = hv_.top->num_owned();
   Run R{s, hv_.top, hv_.comm, n, s->p_ld, hv_.comm->distributed()};
   ready_projection(s, hv_, R);
-  double* buf = (double*)dev::alloc((size_t)2 * s->p_ld * sizeof(double));   // staged: X may be Y or host memory
-  try {
-    if (on_device) dev::d2d(buf, X, n * sizeof(double));
-    else dev::h2d(buf, X, n * sizeof(double));
-    if (which == 0) R.matvec(buf, buf + s->p_ld);
-    else R.prec(buf, buf + s->p_ld);
-    if (on_device) { dev::d2d(Y, buf + s->p_ld, n * sizeof(double)); dev::sync(); }
-    else dev::d2h(Y, buf + s->p_ld, n * sizeof(double));
-  } catch (...) { dev::free(buf); throw; }
-  dev::free(buf);
+  Scratch stage((size_t)2 * s->p_ld);   // staged: X may be Y or host memory
+  double* buf = stage.p;
+  if (on_device) dev::d2d(buf, X, n * sizeof(double));
+  else dev::h2d(buf, X, n * sizeof(double));
+  if (which == 0) R.matvec(buf, buf + s->p_ld);
+  else R.prec(buf, buf + s->p_ld);
+  if (on_device) { dev::d2d(Y, buf + s->p_ld, n * sizeof(double)); dev::sync(); }
+  else dev::d2h(Y, buf + s->p_ld, n * sizeof(double));
 #endif
   SOLVER_END
   return 0;
@@ -1265,17 +1247,14 @@ int hymls_mi_oblique_project(hymls_mi_t* h, int64_t n, int32_t m, const double* 
     HYMLS_CHECK(n >= 1 && m >= 1 && m <= HYMLS_MI_SOLVER_MAX_PROJECTION && ldq >= n && ldp >= n && Q && P && x && y, -2,
                 "oblique_project: need n >= 1, 1 <= m <= 32, ldq and ldp >= n and non-null arrays");
     const int nb = dev::kry_row_grid(n);
-    double* work = (double*)dev::alloc(((size_t)nb * m + (size_t)m * m + dev::KRY_PROJ_MAX) * sizeof(double));
+    Scratch work((size_t)nb * m + (size_t)m * m + dev::KRY_PROJ_MAX);
     dev::KryWork ws{};
-    ws.part = work;
-    ws.h1 = work + (size_t)nb * m + (size_t)m * m;
+    ws.part = work.p;
+    ws.h1 = work.p + (size_t)nb * m + (size_t)m * m;
     double* dG = nullptr;
-    try {
-      if (G) { dG = work + (size_t)nb * m; dev::h2d(dG, G, (size_t)m * m * sizeof(double)); }
-      dev::kry_oblique_project(n, m, Q, ldq, dG, P, ldp, x, y, ws);
-      dev::sync();
-    } catch (...) { dev::free(work); throw; }
-    dev::free(work);
+    if (G) { dG = work.p + (size_t)nb * m; dev::h2d(dG, G, (size_t)m * m * sizeof(double)); }
+    dev::kry_oblique_project(n, m, Q, ldq, dG, P, ldp, x, y, ws);
+    dev::sync();
 #endif
   } catch (const hymls::Error& e) { *hv.err = e.what(); return e.code; }
   catch (const std::exception& e) { *hv.err = e.what(); return -3; }
@@ -1328,13 +1307,11 @@ int hymls_mi_matvec_mv(hymls_mi_t* h, const double* X, int64_t ldx, double* Y, i
       hv.top->matvec_mv(X, ldx, Y, ldy, nvec);
       dev::sync();
     } else {
-      double* buf = (double*)dev::alloc((size_t)2 * nvec * n * sizeof(double));
-      try {
-        for (int v = 0; v < nvec; v++) dev::h2d(buf + (int64_t)v * n, X + (int64_t)v * ldx, n * sizeof(double));
-        hv.top->matvec_mv(buf, n, buf + (int64_t)nvec * n, n, nvec);
-        for (int v = 0; v < nvec; v++) dev::d2h(Y + (int64_t)v * ldy, buf + (int64_t)(nvec + v) * n, n * sizeof(double));
-      } catch (...) { dev::free(buf); throw; }
-      dev::free(buf);
+      Scratch stage((size_t)2 * nvec * n);
+      double* buf = stage.p;
+      for (int v = 0; v < nvec; v++) dev::h2d(buf + (int64_t)v * n, X + (int64_t)v * ldx, n * sizeof(double));
+      hv.top->matvec_mv(buf, n, buf + (int64_t)nvec * n, n, nvec);
+      for (int v = 0; v < nvec; v++) dev::d2h(Y + (int64_t)v * ldy, buf + (int64_t)(nvec + v) * n, n * sizeof(double));
     }
 #endif
   } catch (const hymls::Error& e) { *hv.err = e.what(); return e.code; }
@@ -1362,16 +1339,12 @@ void orthogonalize_mv(const HandleView& hv, int64_t n, int32_t nb, const int32_t
   }
   HYMLS_CHECK(ldh >= kmax, -2, "orthogonalize_mv: ldh smaller than the largest k");
   const size_t per = dev::kry_work_doubles();
-  double* work = (double*)dev::alloc((size_t)nb * per * sizeof(double));
+  Scratch work((size_t)nb * per);
   dev::KryBatch B;
   dev::KryVecBatch sb{};
   B.nb = sb.nb = nb;
   for (int v = 0; v < nb; v++) {
-    dev::KryWork& ws = B.ws[v];
-    ws.part = work + (size_t)v * per;
-    ws.h1 = ws.part + (size_t)dev::KRY_MAXGRID * dev::KRY_KMAX;
-    ws.h2 = ws.h1 + dev::KRY_KMAX;
-    ws.out = ws.h2 + dev::KRY_KMAX;
+    const dev::KryWork ws = B.ws[v] = dev::kry_work_at(work.p + (size_t)v * per);
     B.k[v] = k[v];
     B.V[v] = V + (int64_t)v * vstride;
     B.w[v] = B.dst[v] = W + (int64_t)v * ldw;
@@ -1380,18 +1353,15 @@ void orthogonalize_mv(const HandleView& hv, int64_t n, int32_t nb, const int32_t
     sb.d[v] = ws.out + k[v];
   }
   std::vector<double> hk(dev::KRY_KMAX + 1);
-  try {
-    dev::kry_pass_a_mv(n, ldv, B, F32);
-    dev::kry_pass_b_mv(n, ldv, B, F32);
-    dev::kry_pass_c_mv(n, ldv, B, F32);
-    if (F32 && vnext) dev::kry_round_scale_by_mv(n, sb);
-    for (int v = 0; v < nb; v++) {
-      dev::d2h(hk.data(), B.ws[v].out, (k[v] + 1) * sizeof(double));
-      std::copy(hk.begin(), hk.begin() + k[v], hcoef + (int64_t)v * ldh);
-      wnorm[v] = hk[k[v]];
-    }
-  } catch (...) { dev::free(work); throw; }
-  dev::free(work);
+  dev::kry_pass_a_mv(n, ldv, B, F32);
+  dev::kry_pass_b_mv(n, ldv, B, F32);
+  dev::kry_pass_c_mv(n, ldv, B, F32);
+  if (F32 && vnext) dev::kry_round_scale_by_mv(n, sb);
+  for (int v = 0; v < nb; v++) {
+    dev::d2h(hk.data(), B.ws[v].out, (k[v] + 1) * sizeof(double));
+    std::copy(hk.begin(), hk.begin() + k[v], hcoef + (int64_t)v * ldh);
+    wnorm[v] = hk[k[v]];
+  }
 }
 }  // namespace
 #endif

@@ -48,6 +48,15 @@ struct KryWork {
   double* out;    // [KRY_KMAX + 2]: h1 + h2, then ||w|| and ||w||^2 at out[k], out[k + 1]; dot results at out[0]
 };
 inline size_t kry_work_doubles() { return (size_t)KRY_MAXGRID * KRY_KMAX + 2 * KRY_KMAX + KRY_KMAX + 2; }
+// the four areas of a KryWork in one allocation of kry_work_doubles() doubles at base
+inline KryWork kry_work_at(double* base) {
+  KryWork ws;
+  ws.part = base;
+  ws.h1 = ws.part + (size_t)KRY_MAXGRID * KRY_KMAX;
+  ws.h2 = ws.h1 + KRY_KMAX;
+  ws.out = ws.h2 + KRY_KMAX;
+  return ws;
+}
 
 // pass A: h1 = V^T w over the k columns of V (k <= KRY_KMAX)
 void kry_pass_a(int64_t n, int32_t k, const double* V, int64_t ldv, const double* w, const KryWork& ws);
@@ -103,10 +112,11 @@ void kry_border_product(int64_t n, int32_t m, const double* V, int64_t ldv, cons
 
 // ---- lock-step columns ("MI Lockstep Columns", hymls_mi_solver_set_lockstep): up to KRY_LOCKSTEP_MAX independent
 // columns per launch, the column is blockIdx.y.  Every launcher below gives column v bit for bit what its single-column
-// launcher above gives with the operands of column v: the slice of column v strides by ITS OWN grid (kry_tile_grid(n, k[v]),
-// kry_row_grid(n), vec_grid(n)) and writes that many partials, whatever the other columns of the launch need; the launch
-// itself has the largest grid and the largest LDS size of the batch, and the workgroups of a column beyond its own grid
-// leave before their first barrier.  The operand table is a kernel argument (it lives in the kernarg segment, which the
+// launcher above gives with the operands of column v: in krylov_hip.hip both kernels call one device function (kry_*_body),
+// and the slice of column v strides by ITS OWN grid (kry_tile_grid(n, k[v]), kry_row_grid(n), vec_grid(n)) and writes that
+// many partials, whatever the other columns of the launch need; the launch itself has the largest grid and the largest LDS
+// size of the batch, and the workgroups of a column beyond its own grid leave before their first barrier.
+// The operand table is a kernel argument (it lives in the kernarg segment, which the
 // device reads): no copy per step, and k may change from step to step.  Implemented by krylov_hip.hip and by the
 // test-only tests/krylov_lockstep_sim; krylov.cpp refers to them only under HYMLS_MI_LOCKSTEP_SOLVER.
 constexpr int KRY_LOCKSTEP_MAX = 4;

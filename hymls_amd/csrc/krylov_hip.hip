@@ -15,6 +15,10 @@
 //   k_kry_proj_*        projection vectors: y = x - P (G (Q' x)), the coefficients in two stages and one update pass
 // plus the vector passes of GMRES and CG.  No atomics anywhere: every result is bitwise reproducible.
 //
+// Every pass is written once, as a __device__ body (kry_*_body, kry_column_sum); a __global__ kernel only finds its operands
+// and calls the body.  The single-column kernel passes its arguments and its launch grid, the lock-step kernel (_mv) the
+// operands of column blockIdx.y and that column's own grid: one text, so a batched column cannot drift from its single launch.
+//
 // k_kry_tile and k_kry_rows take the element type of the basis.  With float ("MI Basis Storage" = single) a basis entry
 // is widened when it is used and every product and sum stays FP64; the tile in LDS holds floats (column stride 65
 // floats, krylov.hpp: kry_tile_lds_f32), which is what bounds the workgroups per CU of passes A and B.  Three small
@@ -23,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <string>
+#include <type_traits>
 #include "krylov.hpp"
 
 namespace hymls {
@@ -47,12 +52,39 @@ __device__ inline void block_sum256(double* red) {
   }
   __syncthreads();
 }
+// block_sum256 for MC columns at once (results in red[j][0])
+template <int MC>
+__device__ inline void block_sum256_cols(double (*red)[256]) {
+  const int t = threadIdx.x;
+  for (int st = 128; st > 0; st >>= 1) {
+    __syncthreads();
+    if (t < st) {
+#pragma unroll
+      for (int j = 0; j < MC; j++) red[j][t] += red[j][t + st];
+    }
+  }
+  __syncthreads();
+}
+// stage two of every reduction: the sum of the nb stage-one partials part[b * stride + j] of column j, each thread its
+// partials b = t, t + 256, .. in ascending order, then the fixed tree.  The result is valid on thread 0 alone (only that
+// thread reads red[0], so a caller may go straight on to the next column)
+__device__ inline double kry_column_sum(const double* __restrict__ part, int nb, int64_t stride, int j, double* red) {
+  const int t = threadIdx.x;
+  double s = 0.0;
+  for (int b = t; b < nb; b += 256) s += part[(int64_t)b * stride + j];
+  red[t] = s;
+  block_sum256(red);
+  return t == 0 ? red[0] : 0.0;
+}
+// element c of a per-column table that travels as an int4 kernel argument
+__device__ inline int kry_pick(int4 v, int c) { return c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w)); }
 
 // ---- passes A and B; BT: the element type of the basis (double, or float with "MI Basis Storage" = single).  Every product
-// and sum is FP64: a float entry is widened when it leaves LDS
+// and sum is FP64: a float entry is widened when it leaves LDS.  own: the workgroups that walk the tiles of this column
+// (unsigned, as gridDim.x is: the tile index then advances by the same instructions in both callers)
 template <bool UPD, class BT>
-__global__ void __launch_bounds__(256) k_kry_tile(int64_t n, int k, const BT* __restrict__ V, int64_t ldv, double* w,
-                                                  const double* __restrict__ h1, double* __restrict__ part) {
+__device__ __forceinline__ void kry_tile_body(int64_t n, int k, const BT* __restrict__ V, int64_t ldv, double* w,
+                                              const double* __restrict__ h1, double* __restrict__ part, unsigned own) {
   extern __shared__ double sm[];
   constexpr bool F32 = sizeof(BT) == 4;
   constexpr int T = KRY_TILE, LT = F32 ? KRY_LD_TILE_F32 : KRY_LD_TILE;
@@ -66,7 +98,7 @@ __global__ void __launch_bounds__(256) k_kry_tile(int64_t n, int k, const BT* __
     for (int j = t; j < k; j += 256) hs[j] = h1[j];
   double acc = 0.0;
   const int64_t ntiles = (n + T - 1) / T;
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += own) {
     const int64_t r0 = tile * T;
     const int rows = (int)(n - r0 < T ? n - r0 : T);
     __syncthreads();   // the previous tile is no longer read
@@ -98,12 +130,17 @@ __global__ void __launch_bounds__(256) k_kry_tile(int64_t n, int k, const BT* __
   }
   if (t < k) part[(int64_t)blockIdx.x * k + t] = acc;
 }
+template <bool UPD, class BT>
+__global__ void __launch_bounds__(256) k_kry_tile(int64_t n, int k, const BT* __restrict__ V, int64_t ldv, double* w,
+                                                  const double* __restrict__ h1, double* __restrict__ part) {
+  kry_tile_body<UPD, BT>(n, k, V, ldv, w, h1, part, gridDim.x);
+}
 
-// ---- pass C (NORM) and the solution update
+// ---- pass C (NORM) and the solution update; the launch grid is the column's own grid (kry_row_grid(n))
 template <bool NORM, class BT>
-__global__ void __launch_bounds__(256) k_kry_rows(int64_t n, int k, const BT* __restrict__ V, int64_t ldv,
-                                                  const double* __restrict__ h, const double* w, double* dst,
-                                                  double* __restrict__ part) {
+__device__ __forceinline__ void kry_rows_body(int64_t n, int k, const BT* __restrict__ V, int64_t ldv,
+                                              const double* __restrict__ h, const double* w, double* dst,
+                                              double* __restrict__ part) {
   __shared__ double hs[KRY_KMAX];
   __shared__ double red[256];
   const int t = threadIdx.x;
@@ -129,63 +166,49 @@ __global__ void __launch_bounds__(256) k_kry_rows(int64_t n, int k, const BT* __
     if (t == 0) part[blockIdx.x] = red[0];
   }
 }
+template <bool NORM, class BT>
+__global__ void __launch_bounds__(256) k_kry_rows(int64_t n, int k, const BT* __restrict__ V, int64_t ldv,
+                                                  const double* __restrict__ h, const double* w, double* dst,
+                                                  double* __restrict__ part) {
+  kry_rows_body<NORM, BT>(n, k, V, ldv, h, w, dst, part);
+}
 
 // ---- stage two: dst[j] = sum over the nb partials of column j (and dst2[j] = add[j] + dst[j])
 __global__ void __launch_bounds__(256) k_kry_reduce(const double* __restrict__ part, int nb, int k, double* dst,
                                                     const double* add, double* dst2) {
   __shared__ double red[256];
-  const int j = blockIdx.x, t = threadIdx.x;
-  double s = 0.0;
-  for (int b = t; b < nb; b += 256) s += part[(int64_t)b * k + j];
-  red[t] = s;
-  block_sum256(red);
-  if (t == 0) {
-    dst[j] = red[0];
-    if (add) dst2[j] = add[j] + red[0];
+  const int j = blockIdx.x;
+  const double s = kry_column_sum(part, nb, k, j, red);
+  if (threadIdx.x == 0) {
+    dst[j] = s;
+    if (add) dst2[j] = add[j] + s;
   }
 }
 // dst[0] = sqrt(s), dst[1] = s
 __global__ void __launch_bounds__(256) k_kry_reduce_norm(const double* __restrict__ part, int nb, double* dst) {
   __shared__ double red[256];
-  const int t = threadIdx.x;
-  double s = 0.0;
-  for (int b = t; b < nb; b += 256) s += part[b];
-  red[t] = s;
-  block_sum256(red);
-  if (t == 0) { dst[0] = std::sqrt(red[0]); dst[1] = red[0]; }
+  const double s = kry_column_sum(part, nb, 1, 0, red);
+  if (threadIdx.x == 0) { dst[0] = std::sqrt(s); dst[1] = s; }
 }
 
-// ---- vector passes
-__global__ void __launch_bounds__(256) k_kry_scale_by(int64_t n, double* x, const double* d) {
+// ---- vector passes; a body strides by the launch grid, which is vec_grid(n) for one column and for a batch
+__device__ __forceinline__ void kry_scale_by_body(int64_t n, double* x, const double* d) {
   const double s = *d;
   if (!(s > 0.0)) return;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) x[i] = x[i] / s;
 }
-__global__ void __launch_bounds__(256) k_kry_div(int64_t n, const double* x, double s, double* y) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = x[i] / s;
-}
-// FP32 basis: the widening copy of a column, and the two stores that round a quotient formed in FP64 once
-__global__ void __launch_bounds__(256) k_kry_widen(int64_t n, const float* __restrict__ v, double* __restrict__ t) {
+__device__ __forceinline__ void kry_widen_body(int64_t n, const float* __restrict__ v, double* __restrict__ t) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) t[i] = (double)v[i];
 }
-__global__ void __launch_bounds__(256) k_kry_round_div(int64_t n, const double* __restrict__ x, double s, float* __restrict__ y) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = (float)(x[i] / s);
-}
-__global__ void __launch_bounds__(256) k_kry_round_scale_by(int64_t n, const double* __restrict__ x, const double* d,
-                                                            float* __restrict__ y) {
+__device__ __forceinline__ void kry_round_scale_by_body(int64_t n, const double* __restrict__ x, const double* d,
+                                                        float* __restrict__ y) {
   const double s = *d;
   const bool pos = s > 0.0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
     y[i] = (float)(pos ? x[i] / s : x[i]);
 }
-__global__ void __launch_bounds__(256) k_kry_sub(int64_t n, const double* b, const double* y, double* r) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) r[i] = b[i] - y[i];
-}
-__global__ void __launch_bounds__(256) k_kry_add(int64_t n, const double* x, double* y) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = y[i] + x[i];
-}
-__global__ void __launch_bounds__(256) k_kry_dot(int64_t n, const double* __restrict__ x, const double* __restrict__ y,
-                                                 double* __restrict__ part) {
+__device__ __forceinline__ void kry_dot_body(int64_t n, const double* __restrict__ x, const double* __restrict__ y,
+                                             double* __restrict__ part) {
   __shared__ double red[256];
   double s = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) s += x[i] * y[i];
@@ -193,9 +216,9 @@ __global__ void __launch_bounds__(256) k_kry_dot(int64_t n, const double* __rest
   block_sum256(red);
   if (threadIdx.x == 0) part[blockIdx.x] = red[0];
 }
-__global__ void __launch_bounds__(256) k_kry_cg_xr(int64_t n, double alpha, const double* __restrict__ p,
-                                                   const double* __restrict__ q, double* __restrict__ x,
-                                                   double* __restrict__ r, double* __restrict__ part) {
+__device__ __forceinline__ void kry_cg_xr_body(int64_t n, double alpha, const double* __restrict__ p,
+                                               const double* __restrict__ q, double* __restrict__ x,
+                                               double* __restrict__ r, double* __restrict__ part) {
   __shared__ double red[256];
   double s = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -208,8 +231,42 @@ __global__ void __launch_bounds__(256) k_kry_cg_xr(int64_t n, double alpha, cons
   block_sum256(red);
   if (threadIdx.x == 0) part[blockIdx.x] = red[0];
 }
-__global__ void __launch_bounds__(256) k_kry_cg_p(int64_t n, double beta, const double* __restrict__ z, double* __restrict__ p) {
+__device__ __forceinline__ void kry_cg_p_body(int64_t n, double beta, const double* __restrict__ z, double* __restrict__ p) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = z[i] + beta * p[i];
+}
+
+__global__ void __launch_bounds__(256) k_kry_scale_by(int64_t n, double* x, const double* d) { kry_scale_by_body(n, x, d); }
+__global__ void __launch_bounds__(256) k_kry_div(int64_t n, const double* x, double s, double* y) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = x[i] / s;
+}
+// FP32 basis: the widening copy of a column, and the two stores that round a quotient formed in FP64 once
+__global__ void __launch_bounds__(256) k_kry_widen(int64_t n, const float* __restrict__ v, double* __restrict__ t) {
+  kry_widen_body(n, v, t);
+}
+__global__ void __launch_bounds__(256) k_kry_round_div(int64_t n, const double* __restrict__ x, double s, float* __restrict__ y) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = (float)(x[i] / s);
+}
+__global__ void __launch_bounds__(256) k_kry_round_scale_by(int64_t n, const double* __restrict__ x, const double* d,
+                                                            float* __restrict__ y) {
+  kry_round_scale_by_body(n, x, d, y);
+}
+__global__ void __launch_bounds__(256) k_kry_sub(int64_t n, const double* b, const double* y, double* r) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) r[i] = b[i] - y[i];
+}
+__global__ void __launch_bounds__(256) k_kry_add(int64_t n, const double* x, double* y) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = y[i] + x[i];
+}
+__global__ void __launch_bounds__(256) k_kry_dot(int64_t n, const double* __restrict__ x, const double* __restrict__ y,
+                                                 double* __restrict__ part) {
+  kry_dot_body(n, x, y, part);
+}
+__global__ void __launch_bounds__(256) k_kry_cg_xr(int64_t n, double alpha, const double* __restrict__ p,
+                                                   const double* __restrict__ q, double* __restrict__ x,
+                                                   double* __restrict__ r, double* __restrict__ part) {
+  kry_cg_xr_body(n, alpha, p, q, x, r, part);
+}
+__global__ void __launch_bounds__(256) k_kry_cg_p(int64_t n, double beta, const double* __restrict__ z, double* __restrict__ p) {
+  kry_cg_p_body(n, beta, z, p);
 }
 
 // ---- bordered operator (krylov.hpp: kry_border_product).  Stage one, MC <= KRY_BORDER_CHUNK columns [c0, c0 + MC) of the
@@ -239,14 +296,7 @@ __global__ void __launch_bounds__(256) k_kry_border_rows(int64_t n, int m, int c
   }
 #pragma unroll
   for (int j = 0; j < MC; j++) red[j][t] = acc[j];
-  for (int st = 128; st > 0; st >>= 1) {   // block_sum256 for the MC columns at once
-    __syncthreads();
-    if (t < st) {
-#pragma unroll
-      for (int j = 0; j < MC; j++) red[j][t] += red[j][t + st];
-    }
-  }
-  __syncthreads();
+  block_sum256_cols<MC>(red);
   if (t < MC) part[(int64_t)blockIdx.x * m + c0 + t] = red[t][0];
 }
 // stage two, one workgroup: y[n + j] = (the nb partials of column j, summed as k_kry_reduce does) + sum_l C[j + m l] s_l
@@ -254,14 +304,9 @@ __global__ void __launch_bounds__(256) k_kry_border_tail(const double* __restric
                                                          const double* __restrict__ dC, const double* __restrict__ z,
                                                          double* __restrict__ y) {
   __shared__ double red[256];
-  const int t = threadIdx.x;
   for (int j = 0; j < m; j++) {
-    double s = 0.0;
-    for (int b = t; b < nb; b += 256) s += part[(int64_t)b * m + j];
-    red[t] = s;
-    block_sum256(red);
-    if (t == 0) {
-      double v = red[0];
+    double v = kry_column_sum(part, nb, m, j, red);
+    if (threadIdx.x == 0) {
       if (dC)
         for (int l = 0; l < m; l++) v += dC[j + (int64_t)m * l] * z[n + l];
       y[n + j] = v;
@@ -288,14 +333,7 @@ __global__ void __launch_bounds__(256) k_kry_proj_dots(int64_t n, int m, int c0,
   }
 #pragma unroll
   for (int j = 0; j < MC; j++) red[j][t] = acc[j];
-  for (int st = 128; st > 0; st >>= 1) {   // block_sum256 for the MC columns at once
-    __syncthreads();
-    if (t < st) {
-#pragma unroll
-      for (int j = 0; j < MC; j++) red[j][t] += red[j][t + st];
-    }
-  }
-  __syncthreads();
+  block_sum256_cols<MC>(red);
   if (t < MC) part[(int64_t)blockIdx.x * m + c0 + t] = red[t][0];
 }
 // stage two, one workgroup: c_j = the nb partials of column j, summed as k_kry_reduce does; then thread j forms
@@ -306,11 +344,8 @@ __global__ void __launch_bounds__(256) k_kry_proj_tail(const double* __restrict_
   __shared__ double cs[KRY_PROJ_MAX];
   const int t = threadIdx.x;
   for (int j = 0; j < m; j++) {
-    double s = 0.0;
-    for (int b = t; b < nb; b += 256) s += part[(int64_t)b * m + j];
-    red[t] = s;
-    block_sum256(red);
-    if (t == 0) cs[j] = red[0];
+    const double c = kry_column_sum(part, nb, m, j, red);
+    if (t == 0) cs[j] = c;
   }
   __syncthreads();
   if (t < m) {
@@ -340,195 +375,106 @@ __global__ void __launch_bounds__(256) k_kry_proj_update(int64_t n, int m, const
   }
 }
 
-// ---- lock-step columns (krylov.hpp: KryBatch, KryVecBatch): blockIdx.y is the column.  Each kernel is the body of its
-// single-column kernel above with gridDim.x replaced by the column's own grid `own`: a column strides by the grid its
+// ---- lock-step columns (krylov.hpp: KryBatch, KryVecBatch): blockIdx.y is the column.  Each kernel calls the body of its
+// single-column kernel above with the operands of its column and the column's own grid: a column strides by the grid its
 // single-column launch would have had and writes that many partials, so its sums are added in the same order and give the
-// same bits whatever the other columns of the launch are.  Workgroups past `own` leave before the first barrier.
+// same bits whatever the other columns of the launch are.  Passes A and B: the own grid is `own`, and workgroups past it
+// leave before the first barrier.  Every other pass: the own grid is the same for all columns and is the launch grid.
 template <bool UPD, class BT>
 __global__ void __launch_bounds__(256) k_kry_tile_mv(int64_t n, int64_t ldv, KryBatch B, int4 owns) {
-  extern __shared__ double sm[];
-  constexpr bool F32 = sizeof(BT) == 4;
-  constexpr int T = KRY_TILE, LT = F32 ? KRY_LD_TILE_F32 : KRY_LD_TILE;
   const int c = blockIdx.y;
-  const int k = B.k[c];
-  const int64_t ntiles = (n + T - 1) / T;
-  const int own = c == 0 ? owns.x : (c == 1 ? owns.y : (c == 2 ? owns.z : owns.w));   // kry_tile_grid[_f32](n, k) of this column
+  const int own = kry_pick(owns, c);   // kry_tile_grid[_f32](n, k) of this column
   if ((int)blockIdx.x >= own) return;
-  const BT* __restrict__ V = (const BT*)B.V[c];
-  double* w = B.w[c];
-  const double* __restrict__ h1 = B.ws[c].h1;
-  double* __restrict__ part = B.ws[c].part;
-  BT* Vs = F32 ? (BT*)(sm + T + KRY_KMAX + 4 * T) : (BT*)sm;
-  double* ws = F32 ? sm : sm + (size_t)LT * k;
-  double* hs = ws + T;
-  double* red = hs + KRY_KMAX;
-  const int t = threadIdx.x;
-  if (UPD)
-    for (int j = t; j < k; j += 256) hs[j] = h1[j];
-  double acc = 0.0;
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += own) {
-    const int64_t r0 = tile * T;
-    const int rows = (int)(n - r0 < T ? n - r0 : T);
-    __syncthreads();
-    for (int e = t; e < T * k; e += 256) {
-      const int r = e & (T - 1), j = e / T;
-      Vs[j * LT + r] = r < rows ? V[(int64_t)j * ldv + r0 + r] : (BT)0;
-    }
-    if (t < T) ws[t] = t < rows ? w[r0 + t] : 0.0;
-    __syncthreads();
-    if (UPD) {
-      const int r = t & (T - 1), q = t / T;
-      double s = 0.0;
-      for (int j = q; j < k; j += 4) s += (double)Vs[j * LT + r] * hs[j];
-      red[q * T + r] = s;
-      __syncthreads();
-      if (t < T) {
-        const double v = ws[t] - (((red[t] + red[T + t]) + red[2 * T + t]) + red[3 * T + t]);
-        ws[t] = v;
-        if (t < rows) w[r0 + t] = v;
-      }
-      __syncthreads();
-    }
-    if (t < k) {
-      const BT* cc = Vs + t * LT;
-#pragma unroll 8
-      for (int r = 0; r < T; r++) acc += (double)cc[r] * ws[r];
-    }
-  }
-  if (t < k) part[(int64_t)blockIdx.x * k + t] = acc;
+  kry_tile_body<UPD, BT>(n, B.k[c], (const BT*)B.V[c], ldv, B.w[c], B.ws[c].h1, B.ws[c].part, own);
 }
-
-// pass C of the batch: own grid kry_row_grid(n), the same for every column, is the launch grid
+// pass C of the batch
 template <class BT>
 __global__ void __launch_bounds__(256) k_kry_rows_mv(int64_t n, int64_t ldv, KryBatch B) {
-  __shared__ double hs[KRY_KMAX];
-  __shared__ double red[256];
   const int c = blockIdx.y;
-  const int k = B.k[c];
-  const BT* __restrict__ V = (const BT*)B.V[c];
-  const double* __restrict__ h = B.ws[c].h2;
-  const double* w = B.w[c];
-  double* dst = B.dst[c];
-  const int t = threadIdx.x;
-  for (int j = t; j < k; j += 256) hs[j] = h[j];
-  __syncthreads();
-  double ss = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + t; i < n; i += (int64_t)gridDim.x * 256) {
-    const BT* v = V + i;
-    double s = 0.0;
-#pragma unroll 8
-    for (int j = 0; j < k; j++) s += (double)v[(int64_t)j * ldv] * hs[j];
-    const double x = w[i] - s;
-    dst[i] = x;
-    ss += x * x;
-  }
-  red[t] = ss;
-  block_sum256(red);
-  if (t == 0) B.ws[c].part[blockIdx.x] = red[0];
+  kry_rows_body<true, BT>(n, B.k[c], (const BT*)B.V[c], ldv, B.ws[c].h2, B.w[c], B.dst[c], B.ws[c].part);
 }
 
 // stage two of passes A (UPD false: h1) and B (h2, out = h1 + h2): grid (largest k, columns); nbs[c]: the partials of column c
 template <bool UPD>
 __global__ void __launch_bounds__(256) k_kry_reduce_mv(KryBatch B, int4 nbs) {
   __shared__ double red[256];
-  const int c = blockIdx.y, j = blockIdx.x, t = threadIdx.x;
+  const int c = blockIdx.y, j = blockIdx.x;
   const int k = B.k[c];
   if (j >= k) return;
-  const int nb = c == 0 ? nbs.x : (c == 1 ? nbs.y : (c == 2 ? nbs.z : nbs.w));
-  const double* __restrict__ part = B.ws[c].part;
-  double s = 0.0;
-  for (int b = t; b < nb; b += 256) s += part[(int64_t)b * k + j];
-  red[t] = s;
-  block_sum256(red);
-  if (t == 0) {
-    if (UPD) { B.ws[c].h2[j] = red[0]; B.ws[c].out[j] = B.ws[c].h1[j] + red[0]; }
-    else B.ws[c].h1[j] = red[0];
+  const double s = kry_column_sum(B.ws[c].part, kry_pick(nbs, c), k, j, red);
+  if (threadIdx.x == 0) {
+    if (UPD) { B.ws[c].h2[j] = s; B.ws[c].out[j] = B.ws[c].h1[j] + s; }
+    else B.ws[c].h1[j] = s;
   }
 }
 __global__ void __launch_bounds__(256) k_kry_reduce_norm_mv(KryBatch B, int nb) {
   __shared__ double red[256];
-  const int c = blockIdx.y, t = threadIdx.x;
-  const double* __restrict__ part = B.ws[c].part;
+  const int c = blockIdx.y;
   double* dst = B.ws[c].out + B.k[c];
-  double s = 0.0;
-  for (int b = t; b < nb; b += 256) s += part[b];
-  red[t] = s;
-  block_sum256(red);
-  if (t == 0) { dst[0] = std::sqrt(red[0]); dst[1] = red[0]; }
+  const double s = kry_column_sum(B.ws[c].part, nb, 1, 0, red);
+  if (threadIdx.x == 0) { dst[0] = std::sqrt(s); dst[1] = s; }
 }
 // stage two of the batched dots: out[c][0] = the sum of the nb partials of column c (k_kry_reduce with k = 1)
 __global__ void __launch_bounds__(256) k_kry_reduce1_mv(KryVecBatch B, int nb) {
   __shared__ double red[256];
-  const int c = blockIdx.y, t = threadIdx.x;
-  const double* __restrict__ part = B.part[c];
-  double s = 0.0;
-  for (int b = t; b < nb; b += 256) s += part[b];
-  red[t] = s;
-  block_sum256(red);
-  if (t == 0) B.out[c][0] = red[0];
+  const int c = blockIdx.y;
+  const double s = kry_column_sum(B.part[c], nb, 1, 0, red);
+  if (threadIdx.x == 0) B.out[c][0] = s;
 }
 
 __global__ void __launch_bounds__(256) k_kry_scale_by_mv(int64_t n, KryVecBatch B) {
   const int c = blockIdx.y;
-  double* x = (double*)B.y[c];
-  const double s = *B.d[c];
-  if (!(s > 0.0)) return;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) x[i] = x[i] / s;
+  kry_scale_by_body(n, (double*)B.y[c], B.d[c]);
 }
 __global__ void __launch_bounds__(256) k_kry_widen_mv(int64_t n, KryVecBatch B) {
   const int c = blockIdx.y;
-  const float* __restrict__ v = (const float*)B.a[c];
-  double* __restrict__ t = (double*)B.y[c];
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) t[i] = (double)v[i];
+  kry_widen_body(n, (const float*)B.a[c], (double*)B.y[c]);
 }
 __global__ void __launch_bounds__(256) k_kry_round_scale_by_mv(int64_t n, KryVecBatch B) {
   const int c = blockIdx.y;
-  const double* __restrict__ x = (const double*)B.a[c];
-  float* __restrict__ y = (float*)B.y[c];
-  const double s = *B.d[c];
-  const bool pos = s > 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-    y[i] = (float)(pos ? x[i] / s : x[i]);
+  kry_round_scale_by_body(n, (const double*)B.a[c], B.d[c], (float*)B.y[c]);
 }
 __global__ void __launch_bounds__(256) k_kry_dot_mv(int64_t n, KryVecBatch B) {
-  __shared__ double red[256];
   const int c = blockIdx.y;
-  const double* __restrict__ x = (const double*)B.a[c];
-  const double* __restrict__ y = B.b[c];
-  double s = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) s += x[i] * y[i];
-  red[threadIdx.x] = s;
-  block_sum256(red);
-  if (threadIdx.x == 0) B.part[c][blockIdx.x] = red[0];
+  kry_dot_body(n, (const double*)B.a[c], B.b[c], B.part[c]);
 }
 __global__ void __launch_bounds__(256) k_kry_cg_xr_mv(int64_t n, KryVecBatch B) {
-  __shared__ double red[256];
   const int c = blockIdx.y;
-  const double alpha = B.s[c];
-  const double* __restrict__ p = (const double*)B.a[c];
-  const double* __restrict__ q = B.b[c];
-  double* __restrict__ x = (double*)B.y[c];
-  double* __restrict__ r = B.r[c];
-  double s = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    x[i] = x[i] + alpha * p[i];
-    const double v = r[i] - alpha * q[i];
-    r[i] = v;
-    s += v * v;
-  }
-  red[threadIdx.x] = s;
-  block_sum256(red);
-  if (threadIdx.x == 0) B.part[c][blockIdx.x] = red[0];
+  kry_cg_xr_body(n, B.s[c], (const double*)B.a[c], B.b[c], (double*)B.y[c], B.r[c], B.part[c]);
 }
 __global__ void __launch_bounds__(256) k_kry_cg_p_mv(int64_t n, KryVecBatch B) {
   const int c = blockIdx.y;
-  const double beta = B.s[c];
-  const double* __restrict__ z = (const double*)B.a[c];
-  double* __restrict__ p = (double*)B.y[c];
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = z[i] + beta * p[i];
+  kry_cg_p_body(n, B.s[c], (const double*)B.a[c], (double*)B.y[c]);
 }
 
 static inline void kcheck() { KRY_CHECK(hipGetLastError()); }
+
+// lets the two tile kernels of one basis type (passes A and B; F32: a float tile) use the LDS of KRY_KMAX columns.  The
+// attribute is per device: attr_device is the caller's record of the device that has it (one variable per kernel pair)
+static void allow_tile_lds(const void* pass_a, const void* pass_b, bool F32, int& attr_device) {
+  int devno = 0;
+  KRY_CHECK(hipGetDevice(&devno));
+  if (attr_device == devno) return;
+  const int most = (int)(F32 ? kry_tile_lds_f32(KRY_KMAX) : kry_tile_lds(KRY_KMAX));
+  KRY_CHECK(hipFuncSetAttribute(pass_a, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+  KRY_CHECK(hipFuncSetAttribute(pass_b, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+  attr_device = devno;
+}
+// f(std::integral_constant<int, mc>()) for a chunk of mc = 1..8 columns: the launch of a kernel that has MC as a template parameter
+static_assert(KRY_BORDER_CHUNK == 8 && KRY_PROJ_CHUNK == 8, "for_chunk_width dispatches 1..8 columns");
+template <class F>
+static void for_chunk_width(int mc, F&& f) {
+  switch (mc) {
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    case 4: f(std::integral_constant<int, 4>()); break;
+    case 5: f(std::integral_constant<int, 5>()); break;
+    case 6: f(std::integral_constant<int, 6>()); break;
+    case 7: f(std::integral_constant<int, 7>()); break;
+    default: f(std::integral_constant<int, 8>()); break;
+  }
+}
 
 template <bool UPD, class BT>
 static void tile_pass(int64_t n, int32_t k, const BT* V, int64_t ldv, double* w, const KryWork& ws) {
@@ -536,15 +482,8 @@ static void tile_pass(int64_t n, int32_t k, const BT* V, int64_t ldv, double* w,
   constexpr bool F32 = sizeof(BT) == 4;
   const int nb = F32 ? kry_tile_grid_f32(n, k) : kry_tile_grid(n, k);
   const size_t shm = F32 ? kry_tile_lds_f32(k) : kry_tile_lds(k);
-  static thread_local int attr_device = -1;   // the attribute is per device (and per basis type: one variable each)
-  int devno = 0;
-  KRY_CHECK(hipGetDevice(&devno));
-  if (attr_device != devno) {
-    const int most = (int)(F32 ? kry_tile_lds_f32(KRY_KMAX) : kry_tile_lds(KRY_KMAX));
-    KRY_CHECK(hipFuncSetAttribute((const void*)k_kry_tile<false, BT>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-    KRY_CHECK(hipFuncSetAttribute((const void*)k_kry_tile<true, BT>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-    attr_device = devno;
-  }
+  static thread_local int attr_device = -1;
+  allow_tile_lds((const void*)k_kry_tile<false, BT>, (const void*)k_kry_tile<true, BT>, F32, attr_device);
   hipLaunchKernelGGL((k_kry_tile<UPD, BT>), dim3(nb), dim3(256), shm, kstream(), n, k, V, ldv, w, ws.h1, ws.part);
   kcheck();
   if (UPD) hipLaunchKernelGGL(k_kry_reduce, dim3(k), dim3(256), 0, kstream(), ws.part, nb, k, ws.h2, ws.h1, ws.out);
@@ -639,52 +578,28 @@ void kry_cg_p(int64_t n, double beta, const double* z, double* p) {
   kcheck();
 }
 
-template <int MC>
-static void border_rows(int nb, int64_t n, int32_t m, int c0, const double* V, int64_t ldv, const double* W, int64_t ldw,
-                        const double* z, double* y, const KryWork& ws) {
-  hipLaunchKernelGGL((k_kry_border_rows<MC>), dim3(nb), dim3(256), 0, kstream(), n, m, c0, V, ldv, W, ldw, z, y, ws.part);
-  kcheck();
-}
 void kry_border_product(int64_t n, int32_t m, const double* V, int64_t ldv, const double* W, int64_t ldw, const double* dC,
                         const double* z, double* y, const KryWork& ws) {
   if (n < 1 || m < 1 || m > KRY_BORDER_MAX || ldv < n || ldw < n) throw Error(-2, "border product: n >= 1, 1 <= m <= 32, ldv, ldw >= n");
   const int nb = kry_row_grid(n);
-  for (int c0 = 0; c0 < m; c0 += KRY_BORDER_CHUNK) {
-    switch (std::min(KRY_BORDER_CHUNK, m - c0)) {
-      case 1: border_rows<1>(nb, n, m, c0, V, ldv, W, ldw, z, y, ws); break;
-      case 2: border_rows<2>(nb, n, m, c0, V, ldv, W, ldw, z, y, ws); break;
-      case 3: border_rows<3>(nb, n, m, c0, V, ldv, W, ldw, z, y, ws); break;
-      case 4: border_rows<4>(nb, n, m, c0, V, ldv, W, ldw, z, y, ws); break;
-      case 5: border_rows<5>(nb, n, m, c0, V, ldv, W, ldw, z, y, ws); break;
-      case 6: border_rows<6>(nb, n, m, c0, V, ldv, W, ldw, z, y, ws); break;
-      case 7: border_rows<7>(nb, n, m, c0, V, ldv, W, ldw, z, y, ws); break;
-      default: border_rows<8>(nb, n, m, c0, V, ldv, W, ldw, z, y, ws); break;
-    }
-  }
+  for (int c0 = 0; c0 < m; c0 += KRY_BORDER_CHUNK)
+    for_chunk_width(std::min(KRY_BORDER_CHUNK, m - c0), [&](auto mc) {
+      hipLaunchKernelGGL((k_kry_border_rows<decltype(mc)::value>), dim3(nb), dim3(256), 0, kstream(), n, m, c0, V, ldv, W, ldw, z,
+                         y, ws.part);
+      kcheck();
+    });
   hipLaunchKernelGGL(k_kry_border_tail, dim3(1), dim3(256), 0, kstream(), ws.part, nb, n, m, dC, z, y);
   kcheck();
 }
 
-template <int MC>
-static void proj_dots(int nb, int64_t n, int32_t m, int c0, const double* Q, int64_t ldq, const double* x, const KryWork& ws) {
-  hipLaunchKernelGGL((k_kry_proj_dots<MC>), dim3(nb), dim3(256), 0, kstream(), n, m, c0, Q, ldq, x, ws.part);
-  kcheck();
-}
 void kry_proj_coeffs(int64_t n, int32_t m, const double* Q, int64_t ldq, const double* dG, const double* x, const KryWork& ws) {
   if (n < 1 || m < 1 || m > KRY_PROJ_MAX || ldq < n) throw Error(-2, "oblique projection: n >= 1, 1 <= m <= 32, ldq >= n");
   const int nb = kry_row_grid(n);
-  for (int c0 = 0; c0 < m; c0 += KRY_PROJ_CHUNK) {
-    switch (std::min(KRY_PROJ_CHUNK, m - c0)) {
-      case 1: proj_dots<1>(nb, n, m, c0, Q, ldq, x, ws); break;
-      case 2: proj_dots<2>(nb, n, m, c0, Q, ldq, x, ws); break;
-      case 3: proj_dots<3>(nb, n, m, c0, Q, ldq, x, ws); break;
-      case 4: proj_dots<4>(nb, n, m, c0, Q, ldq, x, ws); break;
-      case 5: proj_dots<5>(nb, n, m, c0, Q, ldq, x, ws); break;
-      case 6: proj_dots<6>(nb, n, m, c0, Q, ldq, x, ws); break;
-      case 7: proj_dots<7>(nb, n, m, c0, Q, ldq, x, ws); break;
-      default: proj_dots<8>(nb, n, m, c0, Q, ldq, x, ws); break;
-    }
-  }
+  for (int c0 = 0; c0 < m; c0 += KRY_PROJ_CHUNK)
+    for_chunk_width(std::min(KRY_PROJ_CHUNK, m - c0), [&](auto mc) {
+      hipLaunchKernelGGL((k_kry_proj_dots<decltype(mc)::value>), dim3(nb), dim3(256), 0, kstream(), n, m, c0, Q, ldq, x, ws.part);
+      kcheck();
+    });
   hipLaunchKernelGGL(k_kry_proj_tail, dim3(1), dim3(256), 0, kstream(), ws.part, nb, m, dG, ws.h1);
   kcheck();
 }
@@ -719,15 +634,8 @@ static void tile_pass_mv(int64_t n, int64_t ldv, const KryBatch& b) {
     kmax = std::max(kmax, (int)b.k[c]);
     shm = std::max(shm, F32 ? kry_tile_lds_f32(b.k[c]) : kry_tile_lds(b.k[c]));
   }
-  static thread_local int attr_device = -1;   // per device and per basis type, as in tile_pass
-  int devno = 0;
-  KRY_CHECK(hipGetDevice(&devno));
-  if (attr_device != devno) {
-    const int most = (int)(F32 ? kry_tile_lds_f32(KRY_KMAX) : kry_tile_lds(KRY_KMAX));
-    KRY_CHECK(hipFuncSetAttribute((const void*)k_kry_tile_mv<false, BT>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-    KRY_CHECK(hipFuncSetAttribute((const void*)k_kry_tile_mv<true, BT>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-    attr_device = devno;
-  }
+  static thread_local int attr_device = -1;
+  allow_tile_lds((const void*)k_kry_tile_mv<false, BT>, (const void*)k_kry_tile_mv<true, BT>, F32, attr_device);
   const int4 owns = make_int4(own[0], own[1], own[2], own[3]);
   hipLaunchKernelGGL((k_kry_tile_mv<UPD, BT>), dim3(grid, b.nb), dim3(256), shm, kstream(), n, ldv, b, owns);
   kcheck();
