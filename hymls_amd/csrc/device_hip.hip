@@ -8,7 +8,8 @@
 //                                factor panels (column-major or packed, rows on consecutive lanes) are streamed once
 //     k_interior_fused_io        the same with a neighbouring vector pass of ApplyInverse in its load / store (FusedIO):
 //                                gather of b1; A12 x2, x1 -= A11 \ y1 and the scatter of x1
-//     k_interior_fused_mv<NV>    the same for 2 or 4 right-hand sides (the panels are streamed once per group)
+//     k_interior_fused_mv<NV>    the same for 2 or 4 right-hand sides (the panels are streamed once per group); the three are
+//                                wrappers of one body, interior_fused_body<PROF, NV, PT, IN, OUT>
 //     k_lvl_fwd / k_lvl_bwd <NV, PT> subdomains too large for LDS: one launch per tree level for all classes, a task is a
 //                                whole small front or a 64-row tile of a large one
 //     k_solve_* / k_panel_*      the coarse direct solver (one class, one member): small fronts per workgroup,
@@ -1958,10 +1959,10 @@ void solve_bwd_level(const PlanD& P, const BatchD& B, const int32_t* list, int32
 // ApplyInverse with nvec > 1 (Epetra_MultiVector; the reference sizes its containers for numvec, src/HYMLS_MatrixBlock.cpp:
 // 335-344): the factor panels, the dominant bytes of a solve, are streamed ONCE for a group of NV columns -- every panel
 // entry loaded is used for NV multiply-adds.  Vectors are column-major with a leading dimension.  The merged level
-// solve and the separator blocks are each written once, as a template over NV that keeps the per-row state
-// (accumulators, LDS vectors) NV times; their single-vector entry points launch NV = 1.  The fused interior solve has a
-// kernel of its own for NV = 2 and 4 (k_interior_fused_mv).  Every column keeps the same accumulators and the same
-// summation tree at every NV, so a column's bits do not depend on its group.
+// solve, the separator blocks and the fused interior solve are each written once, as a template over NV that keeps the
+// per-row state (accumulators, LDS vectors) NV times; their single-vector entry points launch NV = 1 (for the fused solve:
+// the kernels k_interior_fused and k_interior_fused_io, k_interior_fused_mv being NV = 2 and 4 of the same body).  Every
+// column keeps the same accumulators and the same summation tree at every NV, so a column's bits do not depend on its group.
 constexpr size_t LDS_LIMIT_BYTES = 160 * 1024;
 constexpr bool LVL_F32_COLS16_DEFAULT = false;   // tile loops of k_lvl_*<NV, float>: 8 or 16 columns per step
 // widest column group of a launcher (development switch: HYMLS_MI_MV_GROUP_<FUSED|LVL|BLK> = 1, 2 or 4)
@@ -2567,10 +2568,16 @@ __device__ __forceinline__ void fused_spmv_rows(int n, int tid, gptr<int32_t> rp
   }
 }
 // IN / OUT: where the right-hand side comes from and where the solution goes (FusedIO, device.hpp), fixed at compile time
-// so that the plain solve carries none of it.  The body is shared by the two kernels below.
-template <bool PROF, class PT, int IN, int OUT>
+// so that the plain solve carries none of it.
+// NV: the right-hand sides solved together, column v of x at x + v ldx.  The per-row state -- accumulators and the LDS
+// vectors, X[NV][nI] | C[NV][CS] | Fv[NV][FS] | LF -- is kept NV times, and every statement that touches a column runs for
+// v = 0 .. NV - 1 with the additions of the single solve in their order, so a column has the same bits at every NV.  The
+// panel entries, the dominant bytes, are loaded once for the NV columns.  FusedIO and the phase profile (PROF) exist for one
+// column only.  The body is shared by the three kernels below (k_interior_fused, _io, _mv).
+template <bool PROF, int NV, class PT, int IN, int OUT>
 __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__ subs, const PlanD* __restrict__ plans,
-                                                    double* __restrict__ x, long long* __restrict__ prof, const FusedIO io) {
+                                                    double* __restrict__ x, int64_t ldx, long long* __restrict__ prof, const FusedIO io) {
+  static_assert(NV == 1 || (!PROF && IN == 0 && OUT == 0), "FusedIO and the phase profile exist for one column only");
   extern __shared__ double lds[];
   auto ldp = [](gptr<PT> q) { return (double)*q; };
   long long tp[6] = {0, 0, 0, 0, 0, 0}, t0 = 0, tstart = 0;
@@ -2578,12 +2585,14 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
   if (PROF) { t0 = wall_clock64(); tstart = t0; }
   const FusedSub S = subs[blockIdx.x];
   const PlanD P = plans[S.cls];
-  double* X = lds;
-  double* C = lds + P.nI;
-  double* Fv = C + P.contrib_size;
-  // reduction scratch of the k-split levels (<= 128 items, so F uses at most its first 128 entries there): inside F
-  double* R = Fv + 128;
-  FusedFront* LF = (FusedFront*)(Fv + (P.max_level_rows > 384 ? P.max_level_rows : 384));   // compact front descriptors, cached in LDS
+  const int nI = P.nI, CS = P.contrib_size, FS = P.max_level_rows > 384 ? P.max_level_rows : 384;
+  // The LDS vectors: X(v, i) is entry i of column v.  One base and ONE index expression per access -- with a pointer per
+  // column, or with column and entry added in two steps, the 2-column kernels need 81 / 80 VGPRs instead of 76 (DESIGN.md
+  // section 4).  The reduction scratch of the k-split levels (<= 128 items, so a column's F uses at most its first 128
+  // entries there) is inside F, at Fv(v, 128).
+  struct Cols { double* p; int ld; __device__ double& operator()(int v, int i) const { return p[v * ld + i]; } };
+  const Cols X{lds, nI}, C{lds + NV * nI, CS}, Fv{lds + NV * (nI + CS), FS};
+  FusedFront* LF = (FusedFront*)(lds + NV * (nI + CS + FS));   // compact front descriptors, cached in LDS
   const int tid = threadIdx.x;
   for (int i = tid; i < P.nfronts; i += 256) {
     const FrontD G = P.fronts[i];
@@ -2595,26 +2604,28 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
   }
   double* xg = x + S.xoff;
   if (IN == 0) {
-    for (int i = tid; i < P.nI; i += 256) X[i] = xg[i];
+#pragma unroll
+    for (int v = 0; v < NV; v++)
+      for (int i = tid; i < nI; i += 256) X(v, i) = xg[v * ldx + i];
   } else if (IN == 1) {
     // the entry gather of ApplyInverse (k_gather): b through the permutation
     const gptr<int32_t> perm = as_global(io.perm) + S.xoff;
     const gptr<double> b = as_global(io.b);
-    for (int i = tid; i < P.nI; i += 256) X[i] = b[perm[i]];
+    for (int i = tid; i < nI; i += 256) X(0, i) = b[perm[i]];
   } else {
     // y1 = A12 x2 (k_spmv with alpha = 1, beta = 0)
     const gptr<int32_t> a_row = as_global(io.a_row) + S.xoff, a_col = as_global(io.a_col);
     const gptr<double> a_val = as_global(io.a_val), x2 = as_global(io.x2);
     switch (io.a_lanes) {
-      case 1: fused_spmv_rows<1>(P.nI, tid, a_row, a_col, a_val, x2, X); break;
-      case 2: fused_spmv_rows<2>(P.nI, tid, a_row, a_col, a_val, x2, X); break;
-      case 4: fused_spmv_rows<4>(P.nI, tid, a_row, a_col, a_val, x2, X); break;
-      default: fused_spmv_rows<8>(P.nI, tid, a_row, a_col, a_val, x2, X); break;
+      case 1: fused_spmv_rows<1>(nI, tid, a_row, a_col, a_val, x2, X.p); break;
+      case 2: fused_spmv_rows<2>(nI, tid, a_row, a_col, a_val, x2, X.p); break;
+      case 4: fused_spmv_rows<4>(nI, tid, a_row, a_col, a_val, x2, X.p); break;
+      default: fused_spmv_rows<8>(nI, tid, a_row, a_col, a_val, x2, X.p); break;
     }
   }
   __syncthreads();
   tick(0);
-  const gptr<PT> fac = as_global((const PT*)(const void*)S.fac);
+  const gptr<PT> fac = as_global((const PT*)(const void*)S.fac);           // (pointers out of structures: global memory, see as_global)
   const gptr<int32_t> fw_items = as_global(P.fw_items), bw_items = as_global(P.bw_items), fidx = as_global(P.fidx),
                       asm_ptr = as_global(P.asm_ptr), asm_src = as_global(P.asm_src), fw_ptr = as_global(P.fw_ptr), bw_ptr = as_global(P.bw_ptr);
   typedef int v4i __attribute__((ext_vector_type(4)));
@@ -2628,14 +2639,17 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
       const int item = rc.item;
       const FusedFront& F = LF[item >> 16];
       const int r = item & 0xffff;
-      double v = r < F.w ? X[F.c0 + r] : 0.0;
-      if (rc.n != 0xffff) {
 #pragma unroll
-        for (int q = 0; q < 5; q++) if (q < rc.n) v += C[rc.s[q]];
-      } else {
-        for (int t = asm_ptr[F.a_off + r]; t < asm_ptr[F.a_off + r + 1]; t++) v += C[asm_src[t]];
+      for (int v = 0; v < NV; v++) {
+        double val = r < F.w ? X(v, F.c0 + r) : 0.0;
+        if (rc.n != 0xffff) {
+#pragma unroll
+          for (int q = 0; q < 5; q++) if (q < rc.n) val += C(v, rc.s[q]);
+        } else {
+          for (int t = asm_ptr[F.a_off + r]; t < asm_ptr[F.a_off + r + 1]; t++) val += C(v, asm_src[t]);
+        }
+        if (r < F.w) Fv(v, F.lf_off + r) = val; else C(v, F.c_off + r - F.w) = val;   // update rows are assembled in place
       }
-      if (r < F.w) Fv[F.lf_off + r] = v; else C[F.c_off + r - F.w] = v;   // update rows are assembled in place
     }
     __syncthreads();
     tick(1);
@@ -2643,15 +2657,16 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
       for (int it = tid; it < ni; it += 256) {
         const int item = fw_items[ib + it];
         const FusedFront& F = LF[item >> 16];
-        const int r = item & 0xffff, w = F.w;
+        const int r = item & 0xffff, w = F.w, lf = F.lf_off;
         // entry (r, k) of the L-side panel sits at p[c1 * k - tri * k (k + 3) / 2]: plain columns (tri = 0), or the
         // packed strictly-lower triangle for a pivot row of a packed panel (tri = 1)
         int c1, tri;
-        const double* f = Fv + F.lf_off;
         const int kmax = r < w ? r : w;
-        double a[4];
+        double a[4][NV];
 #pragma unroll
-        for (int u = 0; u < 4; u++) a[u] = 0.0;
+        for (int u = 0; u < 4; u++)
+#pragma unroll
+          for (int v = 0; v < NV; v++) a[u][v] = 0.0;
         int k = 0;
         if (F.pad & PAIR_L) {
           // paired panel: the same four columns per trip as two loads, a[u] still gets column k + u; the leftover of up
@@ -2661,14 +2676,21 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
           auto pair_at = [&](int j) { return load_pair<PT>(pp + (c1 * j - tri * 2 * j * j)); };
           for (; k + 3 < kmax; k += 4) {
             const PanelPair<PT> l0 = pair_at(k >> 1), l1 = pair_at((k >> 1) + 1);
-            a[0] += (double)l0.a * f[k]; a[1] += (double)l0.b * f[k + 1]; a[2] += (double)l1.a * f[k + 2]; a[3] += (double)l1.b * f[k + 3];
+#pragma unroll
+            for (int v = 0; v < NV; v++) {
+              a[0][v] += (double)l0.a * Fv(v, lf + k); a[1][v] += (double)l0.b * Fv(v, lf + k + 1);
+              a[2][v] += (double)l1.a * Fv(v, lf + k + 2); a[3][v] += (double)l1.b * Fv(v, lf + k + 3);
+            }
           }
           const bool hp = k + 1 < kmax, hs = (kmax & 1) != 0;
           PanelPair<PT> tl = {}; PT ts = 0;
           if (hp) tl = pair_at(k >> 1);
           if (hs) ts = *ps;
-          if (hp) { a[0] += (double)tl.a * f[k]; a[0] += (double)tl.b * f[k + 1]; }
-          if (hs) a[0] += (double)ts * f[kmax - 1];
+#pragma unroll
+          for (int v = 0; v < NV; v++) {
+            if (hp) { a[0][v] += (double)tl.a * Fv(v, lf + k); a[0][v] += (double)tl.b * Fv(v, lf + k + 1); }
+            if (hs) a[0][v] += (double)ts * Fv(v, lf + kmax - 1);
+          }
         } else {
           const gptr<PT> p = lside(fac + F.lp_off, P.packed, r, w, F.ri, c1, tri);
           for (; k + 3 < kmax; k += 4) {
@@ -2676,45 +2698,64 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
 #pragma unroll
             for (int u = 0; u < 4; u++) l[u] = ldp(p + (c1 * (k + u) - tri * (((k + u) * (k + u + 3)) >> 1)));
 #pragma unroll
-            for (int u = 0; u < 4; u++) a[u] += l[u] * f[k + u];
+            for (int u = 0; u < 4; u++)
+#pragma unroll
+              for (int v = 0; v < NV; v++) a[u][v] += l[u] * Fv(v, lf + k + u);
           }
           tail_batch<3>([&](int u) { return k + u < kmax; },
                         [&](int u) { return ldp(p + (c1 * (k + u) - tri * (((k + u) * (k + u + 3)) >> 1))); },
-                        [&](int u, double l) { a[0] += l * f[k + u]; });
+                        [&](int u, double l) {
+#pragma unroll
+                          for (int v = 0; v < NV; v++) a[0][v] += l * Fv(v, lf + k + u);
+                        });
         }
-        const double sum = (a[0] + a[1]) + (a[2] + a[3]);
-        if (r < w) X[F.c0 + r] = f[r] + sum; else C[F.c_off + r - w] -= sum;
+#pragma unroll
+        for (int v = 0; v < NV; v++) {
+          const double sum = (a[0][v] + a[1][v]) + (a[2][v] + a[3][v]);
+          if (r < w) X(v, F.c0 + r) = Fv(v, lf + r) + sum; else C(v, F.c_off + r - w) -= sum;
+        }
       }
     } else {
       const int RT = ni > 64 ? 128 : 64, KG = 256 / RT;
       const int it = tid % RT, kg = tid / RT;
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+      double a0[NV], a1[NV], a2[NV], a3[NV];
+#pragma unroll
+      for (int v = 0; v < NV; v++) { a0[v] = 0.0; a1[v] = 0.0; a2[v] = 0.0; a3[v] = 0.0; }
       if (it < ni) {
         const int item = fw_items[ib + it];
         const FusedFront& F = LF[item >> 16];
-        const int r = item & 0xffff, w = F.w;
+        const int r = item & 0xffff, w = F.w, lf = F.lf_off;
         int c1, tri;
         const gptr<PT> p = lside(fac + F.lp_off, P.packed, r, w, F.ri, c1, tri);
-        const double* f = Fv + F.lf_off;
         const int kmax = r < w ? r : w;
         auto at = [&](int kk) { return ldp(p + (c1 * kk - tri * ((kk * (kk + 3)) >> 1))); };
         int k = kg;
         for (; k + 3 * KG < kmax; k += 4 * KG) {
           const double l0 = at(k), l1 = at(k + KG), l2 = at(k + 2 * KG), l3 = at(k + 3 * KG);
-          a0 += l0 * f[k]; a1 += l1 * f[k + KG]; a2 += l2 * f[k + 2 * KG]; a3 += l3 * f[k + 3 * KG];
+#pragma unroll
+          for (int v = 0; v < NV; v++) {
+            a0[v] += l0 * Fv(v, lf + k); a1[v] += l1 * Fv(v, lf + k + KG); a2[v] += l2 * Fv(v, lf + k + 2 * KG); a3[v] += l3 * Fv(v, lf + k + 3 * KG);
+          }
         }
         tail_batch<3>([&](int u) { return k + u * KG < kmax; }, [&](int u) { return at(k + u * KG); },
-                      [&](int u, double l) { a0 += l * f[k + u * KG]; });
+                      [&](int u, double l) {
+#pragma unroll
+                        for (int v = 0; v < NV; v++) a0[v] += l * Fv(v, lf + k + u * KG);
+                      });
       }
-      R[kg * RT + it] = (a0 + a1) + (a2 + a3);
+#pragma unroll
+      for (int v = 0; v < NV; v++) Fv(v, 128 + kg * RT + it) = (a0[v] + a1[v]) + (a2[v] + a3[v]);
       __syncthreads();
       if (tid < ni) {
         const int item = fw_items[ib + tid];
         const FusedFront& F = LF[item >> 16];
         const int r = item & 0xffff;
-        double sum = 0.0;
-        for (int g = 0; g < KG; g++) sum += R[g * RT + tid];
-        if (r < F.w) X[F.c0 + r] = Fv[F.lf_off + r] + sum; else C[F.c_off + r - F.w] -= sum;
+#pragma unroll
+        for (int v = 0; v < NV; v++) {
+          double sum = 0.0;
+          for (int g = 0; g < KG; g++) sum += Fv(v, 128 + g * RT + tid);
+          if (r < F.w) X(v, F.c0 + r) = Fv(v, F.lf_off + r) + sum; else C(v, F.c_off + r - F.w) -= sum;
+        }
       }
     }
     __syncthreads();
@@ -2727,25 +2768,31 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
       for (int it = tid; it < ni; it += 256) {
         const int item = bw_items[ib + it];
         const FusedFront& F = LF[item >> 16];
-        const int i = item & 0xffff, w = F.w, ri = F.ri;
+        const int i = item & 0xffff, w = F.w, ri = F.ri, c0 = F.c0;
         // entry (i, k), k >= i, of U11^{-1}: column k of the tall panel, or of the packed upper triangle
         int c1, tri;
         const gptr<PT> p = uside(fac + F.lp_off, P.packed, i, w, ri, c1, tri);
-        const double* Xs = X + F.c0;
-        double a[4];
+        double a[4][NV];
 #pragma unroll
-        for (int u = 0; u < 4; u++) a[u] = 0.0;
+        for (int u = 0; u < 4; u++)
+#pragma unroll
+          for (int v = 0; v < NV; v++) a[u][v] = 0.0;
         int k = i;
         for (; k + 3 < w; k += 4) {
           double l[4];
 #pragma unroll
           for (int u = 0; u < 4; u++) l[u] = ldp(p + (c1 * (k + u) + tri * (((k + u) * (k + u + 1)) >> 1)));
 #pragma unroll
-          for (int u = 0; u < 4; u++) a[u] += l[u] * Xs[k + u];
+          for (int u = 0; u < 4; u++)
+#pragma unroll
+            for (int v = 0; v < NV; v++) a[u][v] += l[u] * X(v, c0 + k + u);
         }
         tail_batch<3>([&](int u) { return k + u < w; },
                       [&](int u) { return ldp(p + (c1 * (k + u) + tri * (((k + u) * (k + u + 1)) >> 1))); },
-                      [&](int u, double l) { a[0] += l * Xs[k + u]; });
+                      [&](int u, double l) {
+#pragma unroll
+                        for (int v = 0; v < NV; v++) a[0][v] += l * X(v, c0 + k + u);
+                      });
         const gptr<int32_t> idx = fidx + F.idx_off + w;
         k = 0;
         if (F.pad & PAIR_Q) {
@@ -2756,14 +2803,20 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
             int id[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) id[u] = idx[k + u];
-            a[0] -= (double)l0.a * X[id[0]]; a[1] -= (double)l0.b * X[id[1]]; a[2] -= (double)l1.a * X[id[2]]; a[3] -= (double)l1.b * X[id[3]];
+#pragma unroll
+            for (int v = 0; v < NV; v++) {
+              a[0][v] -= (double)l0.a * X(v, id[0]); a[1][v] -= (double)l0.b * X(v, id[1]); a[2][v] -= (double)l1.a * X(v, id[2]); a[3][v] -= (double)l1.b * X(v, id[3]);
+            }
           }
           const bool hp = k + 1 < ri, hs = (ri & 1) != 0;
           PanelPair<PT> tl = {}; PT ts = 0; int i0 = 0, i1 = 0, i2 = 0;
           if (hp) { tl = load_pair<PT>(qp + w * k); i0 = idx[k]; i1 = idx[k + 1]; }
           if (hs) { ts = fac[F.q_off + w * (ri - 1) + i]; i2 = idx[ri - 1]; }
-          if (hp) { a[0] -= (double)tl.a * X[i0]; a[0] -= (double)tl.b * X[i1]; }
-          if (hs) a[0] -= (double)ts * X[i2];
+#pragma unroll
+          for (int v = 0; v < NV; v++) {
+            if (hp) { a[0][v] -= (double)tl.a * X(v, i0); a[0][v] -= (double)tl.b * X(v, i1); }
+            if (hs) a[0][v] -= (double)ts * X(v, i2);
+          }
         } else {
           const gptr<PT> qv = fac + F.q_off + i;
           for (; k + 3 < ri; k += 4) {
@@ -2771,103 +2824,141 @@ __device__ __forceinline__ void interior_fused_body(const FusedSub* __restrict__
 #pragma unroll
             for (int u = 0; u < 4; u++) { l[u] = ldp(qv + (int64_t)w * (k + u)); id[u] = idx[k + u]; }
 #pragma unroll
-            for (int u = 0; u < 4; u++) a[u] -= l[u] * X[id[u]];
+            for (int u = 0; u < 4; u++)
+#pragma unroll
+              for (int v = 0; v < NV; v++) a[u][v] -= l[u] * X(v, id[u]);
           }
           tail_batch<3>([&](int u) { return k + u < ri; },
                         [&](int u) { return QEntry{ldp(qv + (int64_t)w * (k + u)), idx[k + u]}; },
-                        [&](int u, QEntry e) { a[0] -= e.q * X[e.id]; });
+                        [&](int u, QEntry e) {
+#pragma unroll
+                          for (int v = 0; v < NV; v++) a[0][v] -= e.q * X(v, e.id);
+                        });
         }
-        Fv[it] = (a[0] + a[1]) + (a[2] + a[3]);     // F is free during the backward sweep
+#pragma unroll
+        for (int v = 0; v < NV; v++) Fv(v, it) = (a[0][v] + a[1][v]) + (a[2][v] + a[3][v]);     // F is free during the backward sweep
       }
       __syncthreads();   // every read of this level's pivot values is done
       for (int it = tid; it < ni; it += 256) {
         const int item = bw_items[ib + it];
-        X[LF[item >> 16].c0 + (item & 0xffff)] = Fv[it];
+        const int dst = LF[item >> 16].c0 + (item & 0xffff);
+#pragma unroll
+        for (int v = 0; v < NV; v++) X(v, dst) = Fv(v, it);
       }
     } else {
       const int RT = ni > 64 ? 128 : 64, KG = 256 / RT;
       const int it = tid % RT, kg = tid / RT;
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+      double a0[NV], a1[NV], a2[NV], a3[NV];
+#pragma unroll
+      for (int v = 0; v < NV; v++) { a0[v] = 0.0; a1[v] = 0.0; a2[v] = 0.0; a3[v] = 0.0; }
       if (it < ni) {
         const int item = bw_items[ib + it];
         const FusedFront& F = LF[item >> 16];
-        const int i = item & 0xffff, w = F.w, ri = F.ri;
+        const int i = item & 0xffff, w = F.w, ri = F.ri, c0 = F.c0;
         int c1, tri;
         const gptr<PT> p = uside(fac + F.lp_off, P.packed, i, w, ri, c1, tri);
-        const double* Xs = X + F.c0;
         auto at = [&](int kk) { return ldp(p + (c1 * kk + tri * ((kk * (kk + 1)) >> 1))); };
         int k = i + kg;
         for (; k + 3 * KG < w; k += 4 * KG) {
           const double l0 = at(k), l1 = at(k + KG), l2 = at(k + 2 * KG), l3 = at(k + 3 * KG);
-          a0 += l0 * Xs[k]; a1 += l1 * Xs[k + KG]; a2 += l2 * Xs[k + 2 * KG]; a3 += l3 * Xs[k + 3 * KG];
+#pragma unroll
+          for (int v = 0; v < NV; v++) {
+            a0[v] += l0 * X(v, c0 + k); a1[v] += l1 * X(v, c0 + k + KG); a2[v] += l2 * X(v, c0 + k + 2 * KG); a3[v] += l3 * X(v, c0 + k + 3 * KG);
+          }
         }
         tail_batch<3>([&](int u) { return k + u * KG < w; }, [&](int u) { return at(k + u * KG); },
-                      [&](int u, double l) { a0 += l * Xs[k + u * KG]; });
+                      [&](int u, double l) {
+#pragma unroll
+                        for (int v = 0; v < NV; v++) a0[v] += l * X(v, c0 + k + u * KG);
+                      });
         const gptr<PT> qv = fac + F.q_off + i;
         const gptr<int32_t> idx = fidx + F.idx_off + w;
         k = kg;
         for (; k + 3 * KG < ri; k += 4 * KG) {
           const double q0 = ldp(qv + (int64_t)w * k), q1 = ldp(qv + (int64_t)w * (k + KG)), q2 = ldp(qv + (int64_t)w * (k + 2 * KG)), q3 = ldp(qv + (int64_t)w * (k + 3 * KG));
           const int i0 = idx[k], i1 = idx[k + KG], i2 = idx[k + 2 * KG], i3 = idx[k + 3 * KG];
-          a0 -= q0 * X[i0]; a1 -= q1 * X[i1]; a2 -= q2 * X[i2]; a3 -= q3 * X[i3];
+#pragma unroll
+          for (int v = 0; v < NV; v++) {
+            a0[v] -= q0 * X(v, i0); a1[v] -= q1 * X(v, i1); a2[v] -= q2 * X(v, i2); a3[v] -= q3 * X(v, i3);
+          }
         }
         tail_batch<3>([&](int u) { return k + u * KG < ri; },
                       [&](int u) { return QEntry{ldp(qv + (int64_t)w * (k + u * KG)), idx[k + u * KG]}; },
-                      [&](int u, QEntry e) { a0 -= e.q * X[e.id]; });
+                      [&](int u, QEntry e) {
+#pragma unroll
+                        for (int v = 0; v < NV; v++) a0[v] -= e.q * X(v, e.id);
+                      });
       }
-      R[kg * RT + it] = (a0 + a1) + (a2 + a3);
+#pragma unroll
+      for (int v = 0; v < NV; v++) Fv(v, 128 + kg * RT + it) = (a0[v] + a1[v]) + (a2[v] + a3[v]);
       __syncthreads();
       if (tid < ni) {
         const int item = bw_items[ib + tid];
-        double sum = 0.0;
-        for (int g = 0; g < KG; g++) sum += R[g * RT + tid];
-        X[LF[item >> 16].c0 + (item & 0xffff)] = sum;
+        const int dst = LF[item >> 16].c0 + (item & 0xffff);
+#pragma unroll
+        for (int v = 0; v < NV; v++) {
+          double sum = 0.0;
+          for (int g = 0; g < KG; g++) sum += Fv(v, 128 + g * RT + tid);
+          X(v, dst) = sum;
+        }
       }
     }
     __syncthreads();
     tick(ni > 128 ? 3 : 4);
   }
   if (OUT == 0) {
-    for (int i = tid; i < P.nI; i += 256) xg[i] = X[i];
+#pragma unroll
+    for (int v = 0; v < NV; v++)
+      for (int i = tid; i < nI; i += 256) xg[v * ldx + i] = X(v, i);
   } else {
     // x1 -= A11 \ y1 (k_axpby with -1, 1: z - X exactly) and the exit scatter (k_scatter)
     const gptr<int32_t> perm = as_global(io.perm) + S.xoff;
     const gptr<double> z = as_global(io.z) + S.xoff;
     const gmptr<double> user = as_global_rw(io.user);
-    for (int i = tid; i < P.nI; i += 256) user[perm[i]] = z[i] - X[i];
+    for (int i = tid; i < nI; i += 256) user[perm[i]] = z[i] - X(0, i);
   }
   if (PROF && tid == 0) {
     tp[5] = wall_clock64() - tstart;
     for (int q = 0; q < 6; q++) prof[(int64_t)blockIdx.x * 8 + q] = tp[q];
     prof[(int64_t)blockIdx.x * 8 + 6] = tstart;
-    prof[(int64_t)blockIdx.x * 8 + 7] = P.nI;
+    prof[(int64_t)blockIdx.x * 8 + 7] = nI;
   }
 }
 // the plain solve, x in place
 template <bool PROF, class PT>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) k_interior_fused(const FusedSub* __restrict__ subs, const PlanD* __restrict__ plans,
                                                          double* __restrict__ x, long long* __restrict__ prof) {
-  interior_fused_body<PROF, PT, 0, 0>(subs, plans, x, prof, FusedIO());
+  interior_fused_body<PROF, 1, PT, 0, 0>(subs, plans, x, 0, prof, FusedIO());
 }
 // the solve with a neighbouring vector pass in its load and / or store: <1, 0> and <2, 1> are the first and the second
 // interior solve of a single-vector ApplyInverse
 template <bool PROF, class PT, int IN, int OUT>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) k_interior_fused_io(const FusedSub* __restrict__ subs, const PlanD* __restrict__ plans,
                                                             double* __restrict__ x, long long* __restrict__ prof, FusedIO io) {
-  interior_fused_body<PROF, PT, IN, OUT>(subs, plans, x, prof, io);
+  interior_fused_body<PROF, 1, PT, IN, OUT>(subs, plans, x, 0, prof, io);
+}
+// The solve for NV = 2 or 4 right-hand sides with leading dimension ldx: a column has the same bits at every NV.
+// (Measured and not kept: 16 / 8 panel entries requested per thread ahead of their use instead of 4 -- the 4-column kernel
+// got 10 % slower; it is not short of bytes in flight.)
+template <int NV, class PT>
+__global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __restrict__ subs, const PlanD* __restrict__ plans,
+                                                            double* __restrict__ x, int64_t ldx) {
+  interior_fused_body<false, NV, PT, 0, 0>(subs, plans, x, ldx, nullptr, FusedIO());
 }
 
+// one launch of a fused solve kernel: a workgroup per subdomain, shm bytes of LDS
+template <class Kernel, class... Args>
+static void launch_fused_grid(Kernel kernel, int32_t nsub, size_t shm, Args... args) {
+  if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+  hipLaunchKernelGGL(kernel, dim3(nsub), dim3(256), shm, g_stream, args...);
+  launch_check();
+}
 template <bool PROF, class PT>
 static void launch_fused_kernel(int32_t nsub, const FusedSub* subs, const PlanD* plans, size_t shm, double* x, long long* prof, const FusedIO& io) {
-  auto go = [&](auto kernel, auto... tail) {
-    if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(kernel, dim3(nsub), dim3(256), shm, g_stream, subs, plans, x, prof, tail...);
-  };
-  if (io.in == 0 && io.out == 0) go(k_interior_fused<PROF, PT>);
-  else if (io.in == 1 && io.out == 0) go(k_interior_fused_io<PROF, PT, 1, 0>, io);
-  else if (io.in == 2 && io.out == 1) go(k_interior_fused_io<PROF, PT, 2, 1>, io);
+  if (io.in == 0 && io.out == 0) launch_fused_grid(k_interior_fused<PROF, PT>, nsub, shm, subs, plans, x, prof);
+  else if (io.in == 1 && io.out == 0) launch_fused_grid(k_interior_fused_io<PROF, PT, 1, 0>, nsub, shm, subs, plans, x, prof, io);
+  else if (io.in == 2 && io.out == 1) launch_fused_grid(k_interior_fused_io<PROF, PT, 2, 1>, nsub, shm, subs, plans, x, prof, io);
   else HYMLS_CHECK(false, -3, "fused interior solve: no kernel for this combination of FusedIO::in and FusedIO::out");
-  launch_check();
 }
 template <class PT>
 static void launch_fused(int32_t nsub, const FusedSub* subs, const PlanD* plans, int32_t lds_doubles, double* x, const FusedIO* iop) {
@@ -2898,284 +2989,6 @@ void interior_solve_fused_f32(int32_t nsub, const FusedSub* subs, const PlanD* p
   launch_fused<float>(nsub, subs, plans, lds_doubles, x, iop);
 }
 
-// The same solve for NV = 2 or 4 right-hand sides: the kernel above with the per-row state (accumulators, LDS vectors)
-// kept NV times and the accumulation order unchanged, so a column has the same bits at every NV (DESIGN.md section 8 on why
-// it is a kernel of its own).
-// (Measured and not kept: 16 / 8 panel entries requested per thread ahead of their use instead of 4 -- the 4-column kernel
-// got 10 % slower; it is not short of bytes in flight.)
-template <int NV, class PT>
-__global__ void __launch_bounds__(256) k_interior_fused_mv(const FusedSub* __restrict__ subs, const PlanD* __restrict__ plans,
-                                                            double* __restrict__ x, int64_t ldx) {
-  extern __shared__ double lds[];
-  const FusedSub S = subs[blockIdx.x];
-  const PlanD P = plans[S.cls];
-  const int nI = P.nI, CS = P.contrib_size, FS = P.max_level_rows > 384 ? P.max_level_rows : 384;
-  double* X = lds;                       // [NV][nI]
-  double* C = X + NV * nI;               // [NV][CS]
-  double* Fv = C + NV * CS;              // [NV][FS]   (reduction scratch of the k-split levels inside, at +128)
-  FusedFront* LF = (FusedFront*)(Fv + NV * FS);
-  const int tid = threadIdx.x;
-  for (int i = tid; i < P.nfronts; i += 256) {
-    const FrontD G = P.fronts[i];
-    FusedFront f;
-    f.c0 = G.c0; f.w = G.w; f.ri = G.ri; f.c_off = G.c_off; f.a_off = G.a_off; f.lf_off = G.lf_off; f.idx_off = G.idx_off;
-    f.pad = P.packed ? G.pair : 0;
-    f.lp_off = G.lp_off; f.q_off = G.q_off;
-    LF[i] = f;
-  }
-  double* xg = x + S.xoff;
-#pragma unroll
-  for (int v = 0; v < NV; v++)
-    for (int i = tid; i < nI; i += 256) X[v * nI + i] = xg[v * ldx + i];
-  __syncthreads();
-  const gptr<PT> fac = as_global((const PT*)(const void*)S.fac);           // (pointers out of structures: global memory, see as_global)
-  const gptr<int32_t> fw_items = as_global(P.fw_items), bw_items = as_global(P.bw_items), fidx = as_global(P.fidx),
-                      asm_ptr = as_global(P.asm_ptr), asm_src = as_global(P.asm_src), fw_ptr = as_global(P.fw_ptr), bw_ptr = as_global(P.bw_ptr);
-  typedef int v4i __attribute__((ext_vector_type(4)));
-  const gptr<v4i> fw_rec = (gptr<v4i>)P.fw_rec;
-  // ---------------- forward
-  for (int lev = 0; lev < P.nlev; lev++) {
-    const int ib = fw_ptr[lev], ni = fw_ptr[lev + 1] - ib;
-    for (int it = tid; it < ni; it += 256) {
-      FwRec rc;
-      { const v4i q = fw_rec[ib + it]; __builtin_memcpy(&rc, &q, 16); }
-      const int item = rc.item;
-      const FusedFront& F = LF[item >> 16];
-      const int r = item & 0xffff;
-#pragma unroll
-      for (int v = 0; v < NV; v++) {
-        const double* Cv = C + v * CS;
-        double val = r < F.w ? X[v * nI + F.c0 + r] : 0.0;
-        if (rc.n != 0xffff) {
-#pragma unroll
-          for (int q = 0; q < 5; q++) if (q < rc.n) val += Cv[rc.s[q]];
-        } else {
-          for (int t = asm_ptr[F.a_off + r]; t < asm_ptr[F.a_off + r + 1]; t++) val += Cv[asm_src[t]];
-        }
-        if (r < F.w) Fv[v * FS + F.lf_off + r] = val; else C[v * CS + F.c_off + r - F.w] = val;
-      }
-    }
-    __syncthreads();
-    if (ni > 128) {
-      for (int it = tid; it < ni; it += 256) {
-        const int item = fw_items[ib + it];
-        const FusedFront& F = LF[item >> 16];
-        const int r = item & 0xffff, w = F.w;
-        int c1, tri;
-        // entry (r, kk) of a paired panel (device.hpp) with 8-byte loads: inside pair kk / 2, or the single entry behind them
-        const bool pl = (F.pad & PAIR_L) != 0;
-        gptr<PT> ps = fac + F.lp_off;
-        const gptr<PT> p = pl ? lside_pair(fac + F.lp_off, r, w, F.ri, c1, tri, ps) : lside(fac + F.lp_off, P.packed, r, w, F.ri, c1, tri);
-        const double* f = Fv + F.lf_off;
-        const int kmax = r < w ? r : w;
-        auto at = [&](int kk) -> PT {
-          if (!pl) return p[c1 * kk - tri * ((kk * (kk + 3)) >> 1)];
-          const int j = kk >> 1;
-          return kk < (kmax & ~1) ? p[c1 * j - tri * 2 * j * j + (kk & 1)] : *ps;
-        };
-        double a[4][NV];    // (the accumulation order of the single-vector kernel: bitwise the same column)
-#pragma unroll
-        for (int u = 0; u < 4; u++)
-#pragma unroll
-          for (int v = 0; v < NV; v++) a[u][v] = 0.0;
-        int k = 0;
-        for (; k + 3 < kmax; k += 4) {
-          double l[4];
-#pragma unroll
-          for (int u = 0; u < 4; u++) l[u] = at(k + u);
-#pragma unroll
-          for (int u = 0; u < 4; u++)
-#pragma unroll
-            for (int v = 0; v < NV; v++) a[u][v] += l[u] * f[v * FS + k + u];
-        }
-        tail_batch<3>([&](int u) { return k + u < kmax; },
-                      [&](int u) { return (double)at(k + u); },
-                      [&](int u, double l) {
-#pragma unroll
-                        for (int v = 0; v < NV; v++) a[0][v] += l * f[v * FS + k + u];
-                      });
-#pragma unroll
-        for (int v = 0; v < NV; v++) {
-          const double sum = (a[0][v] + a[1][v]) + (a[2][v] + a[3][v]);
-          if (r < w) X[v * nI + F.c0 + r] = f[v * FS + r] + sum; else C[v * CS + F.c_off + r - w] -= sum;
-        }
-      }
-    } else {
-      const int RT = ni > 64 ? 128 : 64, KG = 256 / RT;
-      const int it = tid % RT, kg = tid / RT;
-      double a0[NV], a1[NV], a2[NV], a3[NV];
-#pragma unroll
-      for (int v = 0; v < NV; v++) { a0[v] = 0.0; a1[v] = 0.0; a2[v] = 0.0; a3[v] = 0.0; }
-      if (it < ni) {
-        const int item = fw_items[ib + it];
-        const FusedFront& F = LF[item >> 16];
-        const int r = item & 0xffff, w = F.w;
-        int c1, tri;
-        const gptr<PT> p = lside(fac + F.lp_off, P.packed, r, w, F.ri, c1, tri);
-        const double* f = Fv + F.lf_off;
-        const int kmax = r < w ? r : w;
-        auto at = [&](int kk) { return p[c1 * kk - tri * ((kk * (kk + 3)) >> 1)]; };
-        int k = kg;
-        for (; k + 3 * KG < kmax; k += 4 * KG) {
-          const double l0 = at(k), l1 = at(k + KG), l2 = at(k + 2 * KG), l3 = at(k + 3 * KG);
-#pragma unroll
-          for (int v = 0; v < NV; v++) {
-            a0[v] += l0 * f[v * FS + k]; a1[v] += l1 * f[v * FS + k + KG];
-            a2[v] += l2 * f[v * FS + k + 2 * KG]; a3[v] += l3 * f[v * FS + k + 3 * KG];
-          }
-        }
-        tail_batch<3>([&](int u) { return k + u * KG < kmax; }, [&](int u) { return (double)at(k + u * KG); },
-                      [&](int u, double l) {
-#pragma unroll
-                        for (int v = 0; v < NV; v++) a0[v] += l * f[v * FS + k + u * KG];
-                      });
-      }
-#pragma unroll
-      for (int v = 0; v < NV; v++) Fv[v * FS + 128 + kg * RT + it] = (a0[v] + a1[v]) + (a2[v] + a3[v]);
-      __syncthreads();
-      if (tid < ni) {
-        const int item = fw_items[ib + tid];
-        const FusedFront& F = LF[item >> 16];
-        const int r = item & 0xffff;
-#pragma unroll
-        for (int v = 0; v < NV; v++) {
-          double sum = 0.0;
-          for (int g = 0; g < KG; g++) sum += Fv[v * FS + 128 + g * RT + tid];
-          if (r < F.w) X[v * nI + F.c0 + r] = Fv[v * FS + F.lf_off + r] + sum; else C[v * CS + F.c_off + r - F.w] -= sum;
-        }
-      }
-    }
-    __syncthreads();
-  }
-  // ---------------- backward
-  for (int lev = P.nlev - 1; lev >= 0; lev--) {
-    const int ib = bw_ptr[lev], ni = bw_ptr[lev + 1] - ib;
-    if (ni > 128) {
-      for (int it = tid; it < ni; it += 256) {
-        const int item = bw_items[ib + it];
-        const FusedFront& F = LF[item >> 16];
-        const int i = item & 0xffff, w = F.w, ri = F.ri;
-        int c1, tri;
-        const gptr<PT> p = uside(fac + F.lp_off, P.packed, i, w, ri, c1, tri);
-        const double* Xs = X + F.c0;
-        double a[4][NV];
-#pragma unroll
-        for (int u = 0; u < 4; u++)
-#pragma unroll
-          for (int v = 0; v < NV; v++) a[u][v] = 0.0;
-        int k = i;
-        for (; k + 3 < w; k += 4) {
-          double l[4];
-#pragma unroll
-          for (int u = 0; u < 4; u++) l[u] = p[c1 * (k + u) + tri * (((k + u) * (k + u + 1)) >> 1)];
-#pragma unroll
-          for (int u = 0; u < 4; u++)
-#pragma unroll
-            for (int v = 0; v < NV; v++) a[u][v] += l[u] * Xs[v * nI + k + u];
-        }
-        tail_batch<3>([&](int u) { return k + u < w; },
-                      [&](int u) { return (double)p[c1 * (k + u) + tri * (((k + u) * (k + u + 1)) >> 1)]; },
-                      [&](int u, double l) {
-#pragma unroll
-                        for (int v = 0; v < NV; v++) a[0][v] += l * Xs[v * nI + k + u];
-                      });
-        const gptr<PT> qv = fac + F.q_off + i;
-        const gptr<int32_t> idx = fidx + F.idx_off + w;
-        const bool pq = (F.pad & PAIR_Q) != 0;   // entry (i, kk) of a paired Q (device.hpp)
-        auto qat = [&](int kk) -> PT { return pq && kk < (ri & ~1) ? qv[2 * w * (kk >> 1) + i + (kk & 1)] : qv[(int64_t)w * kk]; };
-        k = 0;
-        for (; k + 3 < ri; k += 4) {
-          double l[4]; int id[4];
-#pragma unroll
-          for (int u = 0; u < 4; u++) { l[u] = qat(k + u); id[u] = idx[k + u]; }
-#pragma unroll
-          for (int u = 0; u < 4; u++)
-#pragma unroll
-            for (int v = 0; v < NV; v++) a[u][v] -= l[u] * X[v * nI + id[u]];
-        }
-        tail_batch<3>([&](int u) { return k + u < ri; },
-                      [&](int u) { return QEntry{(double)qat(k + u), idx[k + u]}; },
-                      [&](int u, QEntry e) {
-#pragma unroll
-                        for (int v = 0; v < NV; v++) a[0][v] -= e.q * X[v * nI + e.id];
-                      });
-#pragma unroll
-        for (int v = 0; v < NV; v++) Fv[v * FS + it] = (a[0][v] + a[1][v]) + (a[2][v] + a[3][v]);
-      }
-      __syncthreads();
-      for (int it = tid; it < ni; it += 256) {
-        const int item = bw_items[ib + it];
-        const int dst = LF[item >> 16].c0 + (item & 0xffff);
-#pragma unroll
-        for (int v = 0; v < NV; v++) X[v * nI + dst] = Fv[v * FS + it];
-      }
-    } else {
-      const int RT = ni > 64 ? 128 : 64, KG = 256 / RT;
-      const int it = tid % RT, kg = tid / RT;
-      double a0[NV], a1[NV], a2[NV], a3[NV];
-#pragma unroll
-      for (int v = 0; v < NV; v++) { a0[v] = 0.0; a1[v] = 0.0; a2[v] = 0.0; a3[v] = 0.0; }
-      if (it < ni) {
-        const int item = bw_items[ib + it];
-        const FusedFront& F = LF[item >> 16];
-        const int i = item & 0xffff, w = F.w, ri = F.ri;
-        int c1, tri;
-        const gptr<PT> p = uside(fac + F.lp_off, P.packed, i, w, ri, c1, tri);
-        const double* Xs = X + F.c0;
-        auto at = [&](int kk) { return p[c1 * kk + tri * ((kk * (kk + 1)) >> 1)]; };
-        int k = i + kg;
-        for (; k + 3 * KG < w; k += 4 * KG) {
-          const double l0 = at(k), l1 = at(k + KG), l2 = at(k + 2 * KG), l3 = at(k + 3 * KG);
-#pragma unroll
-          for (int v = 0; v < NV; v++) {
-            a0[v] += l0 * Xs[v * nI + k]; a1[v] += l1 * Xs[v * nI + k + KG];
-            a2[v] += l2 * Xs[v * nI + k + 2 * KG]; a3[v] += l3 * Xs[v * nI + k + 3 * KG];
-          }
-        }
-        tail_batch<3>([&](int u) { return k + u * KG < w; }, [&](int u) { return (double)at(k + u * KG); },
-                      [&](int u, double l) {
-#pragma unroll
-                        for (int v = 0; v < NV; v++) a0[v] += l * Xs[v * nI + k + u * KG];
-                      });
-        const gptr<PT> qv = fac + F.q_off + i;
-        const gptr<int32_t> idx = fidx + F.idx_off + w;
-        k = kg;
-        for (; k + 3 * KG < ri; k += 4 * KG) {
-          const double q0 = qv[(int64_t)w * k], q1 = qv[(int64_t)w * (k + KG)], q2 = qv[(int64_t)w * (k + 2 * KG)], q3 = qv[(int64_t)w * (k + 3 * KG)];
-          const int i0 = idx[k], i1 = idx[k + KG], i2 = idx[k + 2 * KG], i3 = idx[k + 3 * KG];
-#pragma unroll
-          for (int v = 0; v < NV; v++) {
-            a0[v] -= q0 * X[v * nI + i0]; a1[v] -= q1 * X[v * nI + i1]; a2[v] -= q2 * X[v * nI + i2]; a3[v] -= q3 * X[v * nI + i3];
-          }
-        }
-        tail_batch<3>([&](int u) { return k + u * KG < ri; },
-                      [&](int u) { return QEntry{(double)qv[(int64_t)w * (k + u * KG)], idx[k + u * KG]}; },
-                      [&](int u, QEntry e) {
-#pragma unroll
-                        for (int v = 0; v < NV; v++) a0[v] -= e.q * X[v * nI + e.id];
-                      });
-      }
-#pragma unroll
-      for (int v = 0; v < NV; v++) Fv[v * FS + 128 + kg * RT + it] = (a0[v] + a1[v]) + (a2[v] + a3[v]);
-      __syncthreads();
-      if (tid < ni) {
-        const int item = bw_items[ib + tid];
-        const int dst = LF[item >> 16].c0 + (item & 0xffff);
-#pragma unroll
-        for (int v = 0; v < NV; v++) {
-          double sum = 0.0;
-          for (int g = 0; g < KG; g++) sum += Fv[v * FS + 128 + g * RT + tid];
-          X[v * nI + dst] = sum;
-        }
-      }
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int v = 0; v < NV; v++)
-    for (int i = tid; i < nI; i += 256) xg[v * ldx + i] = X[v * nI + i];
-}
-
 // nv columns in groups.  lds_doubles: LDS need of one vector; front_doubles: the part of it that holds the front
 // descriptors (not replicated)
 template <class PT>
@@ -3189,10 +3002,7 @@ static void fused_mv_groups(int32_t nsub, const FusedSub* subs, const PlanD* pla
     if constexpr (NV == 1) {
       launch_fused<PT>(nsub, subs, plans, lds_doubles, xv, nullptr);
     } else {
-      const size_t shm = per * NV + fixed;
-      if (shm > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)k_interior_fused_mv<NV, PT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-      hipLaunchKernelGGL((k_interior_fused_mv<NV, PT>), dim3(nsub), dim3(256), shm, g_stream, subs, plans, xv, ldx);
-      launch_check();
+      launch_fused_grid(k_interior_fused_mv<NV, PT>, nsub, per * NV + fixed, subs, plans, xv, ldx);
     }
   });
 }

@@ -1,7 +1,8 @@
 """A/B of two builds of the library in ONE process on one GPU (development aid): both preconditioners are set up side by
 side (ctypes loads each .so with RTLD_LOCAL), then ApplyInverse alternates between them, so that clocks and
-temperature are the same for both.   python tools/ab_apply.py libA.so libB.so [N=256] [levels=2] [problem=Stokes]
-Environment switches that a library reads when a handle is created can differ: AB_ENV_A="K=V,K2=V2" AB_ENV_B=...
+temperature are the same for both.   python tools/ab_apply.py libA.so libB.so [N=256] [levels=2] [problem=Stokes] [nrhs=1]
+With nrhs = 2 or 4 ApplyInverse gets a block of that many columns (the multi-vector apply; the interior solves are then
+k_interior_fused_mv<2> / <4>).  Environment switches that a library reads when a handle is created can differ: AB_ENV_A="K=V,K2=V2" AB_ENV_B=...
 (two copies of one .so file give two independent instances)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -14,6 +15,7 @@ libs = [os.path.abspath(a) for a in sys.argv[1:3]]
 n = int(sys.argv[3]) if len(sys.argv) > 3 else 256
 levels = int(sys.argv[4]) if len(sys.argv) > 4 else 2
 problem = sys.argv[5] if len(sys.argv) > 5 else "Stokes"
+nrhs = int(sys.argv[6]) if len(sys.argv) > 6 else 1
 prm = {"Problem": {"Equations": "Stokes-C", "Dimension": 3, "nx": n, "ny": n, "nz": n},
        "Preconditioner": {"Separator Length": 8, "Number of Levels": levels, "Partitioner": "Skew Cartesian"}}
 P = []
@@ -46,6 +48,8 @@ for q, path in enumerate(libs):
 N = K[0].size - 1
 g = torch.Generator(device="cuda"); g.manual_seed(1)
 b = torch.rand(N, dtype=torch.float64, device="cuda", generator=g) * 2 - 1
+if nrhs > 1:   # (nrhs, N) row-major = column-major (N, nrhs); column 0 is the single run's b
+    b = torch.cat([b[None], torch.rand((nrhs - 1, N), dtype=torch.float64, device="cuda", generator=g) * 2 - 1])
 x = [torch.empty_like(b), torch.empty_like(b)]
 for _ in range(3):
     for q in (0, 1):
