@@ -34,6 +34,12 @@
 // dev::kry_oblique_project (krylov.hpp).  The preconditioner has two forms that are equal in exact arithmetic: the literal
 // one applies M^{-1} twice as the reference does, the folded one applies it once and subtracts Z (H^{-1} (BV' M^{-1} x))
 // with Z = M^{-1} BV formed once per Compute.  One GPU, one column at a time.
+//
+// Shifted operator (hymls_mi_solver_set_shift and _set_mass_matrix, under HYMLS_MI_SHIFTED_SOLVER; the reference's
+// BaseSolver::setShift / SetMassMatrix with HYMLS::ShiftedOperator): with (a, b) != (1, 0) every K x of the solve -- the plain,
+// the projected and the bordered operator, the explicit residuals, CG, the lock-step group's product -- is a K x + b B x from
+// one dev::kry_shifted_product (Run::product), B the mass matrix or the identity.  The preconditioner stays that of K.
+// With (1, 0) nothing changes, whether or not a mass matrix is set.  One GPU.
 #include "../../include/hymls_mi_solver.h"
 #include "capi_internal.hpp"
 #include "krylov.hpp"
@@ -95,6 +101,13 @@ struct hymls_mi_solver {
   double *pV = nullptr, *pBV = nullptr, *pZ = nullptr, *p_tmp = nullptr, *pG = nullptr;
   dev::KryWork pws{};              // part[kry_row_grid(n) * m], h1[m]
   int p_compute = -1;              // hymls_mi_num_compute of the handle when Z and H were formed (-1: not yet)
+  // shifted operator a K + b B (hymls_mi_solver_set_shift, hymls_mi_solver_set_mass_matrix): the pair, and the device copy of
+  // B in one block (values, rowptr, colind), allocated when B is set; without B the identity
+  double sh_a = 1.0, sh_b = 0.0;
+  int64_t b_n = 0, b_nnz = 0;
+  void* b_buf = nullptr;
+  const int32_t *b_rp = nullptr, *b_col = nullptr;
+  const double* b_val = nullptr;
 };
 
 namespace {
@@ -129,8 +142,27 @@ struct Run {
   const double *pV = nullptr, *pBV = nullptr, *pZ = nullptr, *pG = nullptr;
   double* ptmp = nullptr;
   dev::KryWork pws{};
+  // shifted operator (shifted: (a, b) != (1, 0)): the pair and the solver's device copy of B (null: the identity)
+  bool shifted = false;
+  double sa = 1.0, sb = 0.0;
+  const int32_t *brp = nullptr, *bcol = nullptr;
+  const double* bval = nullptr;
 
   void mark(int phase, bool begin) { if (s->profiling) dev::kry_mark(s->timer, phase, begin); }
+  // out(:, v) = K in(:, v), or (a K + b B) in(:, v) with a shift, on the rows of K; in and out must not overlap
+  void product(const double* in, double* out) {
+#ifdef HYMLS_MI_SHIFTED_SOLVER
+    if (shifted) { product_mv(in, nh, out, nh, 1); return; }
+#endif
+    L->matvec(in, out);
+  }
+#ifdef HYMLS_MI_SHIFTED_SOLVER
+  // (the lanes per row are those of LevelSolver::matvec, so the row sums of K are bitwise those of K x)
+  void product_mv(const double* in, int64_t ldi, double* out, int64_t ldo, int nv) {
+    const LevelSolver::DeviceCsr K = L->k_device();
+    dev::kry_shifted_product(K.n, K.rowptr, K.col, K.val, -1, brp, bcol, bval, sa, sb, in, ldi, out, ldo, nv);
+  }
+#endif
   // the seven vectors of a column, in one block of 7 ld doubles
   void bind_vectors(double* v) {
     x = v; r = v + ld; w = v + 2 * ld; t = v + 3 * ld; p = v + 4 * ld; prev = v + 5 * ld; bst = v + 6 * ld;
@@ -168,13 +200,13 @@ struct Run {
   void matvec(const double* in, double* out) {
     mark(2, true);
 #ifdef HYMLS_MI_PROJECTED_SOLVER
-    if (pm > 0) {                  // (I - BV V') K (I - V BV') in
+    if (pm > 0) {                  // (I - BV V') K (I - V BV') in  (with a shift: a K + b B in the place of K, here and below)
       dev::kry_oblique_project(n, pm, pBV, pld, nullptr, pV, pld, in, ptmp, pws);
-      L->matvec(ptmp, out);
+      product(ptmp, out);
       dev::kry_oblique_project(n, pm, pV, pld, nullptr, pBV, pld, out, out, pws);
     } else
 #endif
-    L->matvec(in, out);
+    product(in, out);
 #ifdef HYMLS_MI_BORDERED_SOLVER
     if (bm > 0) dev::kry_border_product(nh, bm, L->border_v(), nh, L->border_w(), nh, dC, in, out, ws);
 #endif
@@ -492,6 +524,11 @@ struct Lockstep {
   }
   void matvec_mv(int which_in, int which_out, int na) {
     mark(2, true);
+#ifdef HYMLS_MI_SHIFTED_SOLVER
+    // with a shift: K and B are read once per group, and column v has the bits of Run::product on it
+    if (R[0].shifted) R[0].product_mv(stage(which_in, 0), ld, stage(which_out, 0), ld, na);
+    else
+#endif
     L->matvec_mv(stage(which_in, 0), ld, stage(which_out, 0), ld, na);
     mark(2, false);
   }
@@ -660,6 +697,21 @@ void free_projection(hymls_mi_solver* s) {
   s->pm = 0; s->p_n = s->p_ld = 0; s->p_same = true; s->p_compute = -1;
 }
 
+void free_mass(hymls_mi_solver* s) {
+  dev::free(s->b_buf);
+  s->b_buf = nullptr;
+  s->b_rp = s->b_col = nullptr;
+  s->b_val = nullptr;
+  s->b_n = s->b_nnz = 0;
+}
+
+// hands the shift and the mass matrix of the solver to a Run; (1, 0) leaves the Run on the plain K x, with or without B
+void bind_shift(const hymls_mi_solver* s, Run& R) {
+  R.shifted = !(s->sh_a == 1.0 && s->sh_b == 0.0);
+  R.sa = s->sh_a; R.sb = s->sh_b;
+  R.brp = s->b_rp; R.bcol = s->b_col; R.bval = s->b_val;
+}
+
 #ifdef HYMLS_MI_PROJECTED_SOLVER
 // hands the projection of the solver to a Run
 void bind_projection(const hymls_mi_solver* s, Run& R) {
@@ -821,6 +873,8 @@ int solve_columns(hymls_mi_solver* s, const HandleView& hv_, int bm, const doubl
   }
   Run R{s, L, hv_.comm, n, s->ld, hv_.comm->distributed()};
   R.nh = nh;
+  bind_shift(s, R);
+  HYMLS_CHECK(!R.shifted || !s->b_buf || s->b_n == nh, -2, "the mass matrix does not have the row count of the handle");
   if (bm > 0) {
     if (!s->bc) s->bc = (double*)dev::alloc((size_t)HYMLS_MI_SOLVER_MAX_BORDER * HYMLS_MI_SOLVER_MAX_BORDER * sizeof(double));
     dev::h2d(s->bc, L->border_c(), (size_t)bm * bm * sizeof(double));
@@ -989,7 +1043,8 @@ int hymls_mi_solver_solve(hymls_mi_solver_t* s, const double* B, int64_t ldb, do
   HYMLS_CHECK(s->lockstep == 1, -99, "this build has no batched Krylov launchers (a test-only simulator without them)");
 #endif
   HYMLS_CHECK(s->pm == 0 || !hv_.comm->distributed(), -99, "solve with projection vectors: one GPU only (sharded handles are not supported)");
-  status = solve_columns(s, hv_, 0, B, ldb, nullptr, X, ldx, nullptr, nvec, on_device);
+  HYMLS_CHECK((s->sh_a == 1.0 && s->sh_b == 0.0) || !hv_.comm->distributed(), -99,
+              "solve with a shift: one GPU only (sharded handles are not supported)");  status = solve_columns(s, hv_, 0, B, ldb, nullptr, X, ldx, nullptr, nvec, on_device);
   SOLVER_END
   return status;
 }
@@ -1220,6 +1275,8 @@ int hymls_mi_solver_apply_projected(hymls_mi_solver_t* s, int which, const doubl
   HYMLS_CHECK((which == 0 || which == 1) && X && Y, -2, "apply_projected: which is 0 (operator) or 1 (preconditioner); X and Y non-null");
   const int64_t n = hv_.top->num_owned();
   Run R{s, hv_.top, hv_.comm, n, s->p_ld, hv_.comm->distributed()};
+  R.nh = n;
+  bind_shift(s, R);
   ready_projection(s, hv_, R);
   Scratch stage((size_t)2 * s->p_ld);   // staged: X may be Y or host memory
   double* buf = stage.p;
@@ -1254,6 +1311,169 @@ int hymls_mi_oblique_project(hymls_mi_t* h, int64_t n, int32_t m, const double* 
     double* dG = nullptr;
     if (G) { dG = work.p + (size_t)nb * m; dev::h2d(dG, G, (size_t)m * m * sizeof(double)); }
     dev::kry_oblique_project(n, m, Q, ldq, dG, P, ldp, x, y, ws);
+    dev::sync();
+#endif
+  } catch (const hymls::Error& e) { *hv.err = e.what(); return e.code; }
+  catch (const std::exception& e) { *hv.err = e.what(); return -3; }
+  return 0;
+}
+
+#ifndef HYMLS_MI_SHIFTED_SOLVER
+#define SHIFT_MISSING throw hymls::Error(-99, "this build has no shifted product kernel (a test-only simulator without it)")
+#else
+namespace {
+// do the nvec columns of n doubles at X (leading dimension ldx) and at Y (ldy) share a byte?
+bool columns_overlap(const double* X, int64_t ldx, const double* Y, int64_t ldy, int64_t n, int nvec) {
+  const uintptr_t x0 = (uintptr_t)X, x1 = x0 + ((size_t)(nvec - 1) * ldx + n) * sizeof(double);
+  const uintptr_t y0 = (uintptr_t)Y, y1 = y0 + ((size_t)(nvec - 1) * ldy + n) * sizeof(double);
+  return x0 < y1 && y0 < x1;
+}
+}  // namespace
+#endif
+
+int hymls_mi_solver_set_mass_matrix(hymls_mi_solver_t* s, int64_t n, const int32_t* rowptr, const int32_t* colind,
+                                    const double* values, int on_device) {
+  if (!s) return -2;
+  SOLVER_BEGIN
+#ifndef HYMLS_MI_SHIFTED_SOLVER
+  (void)n; (void)rowptr; (void)colind; (void)values; (void)on_device;
+  SHIFT_MISSING;
+#else
+  if (s->b_buf) dev::sync();       // whatever follows, the matrix set before is gone
+  free_mass(s);
+  if (!rowptr) return 0;           // the identity from the next solve on
+  HYMLS_CHECK(hv_.top, -1, "set_mass_matrix needs an initialized handle (its row count)");
+  HYMLS_CHECK(n == hv_.top->num_owned(), -2, "set_mass_matrix: n is not the row count of the handle");
+  // every index is checked on the host before a kernel reads it; device input: rowptr and colind are copied back once
+  std::vector<int32_t> hrp, hcol;
+  const int32_t* rp = rowptr;
+  if (on_device) { hrp.resize(n + 1); dev::d2h(hrp.data(), rowptr, (size_t)(n + 1) * sizeof(int32_t)); rp = hrp.data(); }
+  HYMLS_CHECK(rp[0] == 0, -2, "set_mass_matrix: rowptr[0] is not 0");
+  for (int64_t i = 0; i < n; i++)
+    if (rp[i + 1] < rp[i]) {
+      char buf[128];
+      std::snprintf(buf, sizeof buf, "set_mass_matrix: rowptr decreases at row %lld (%d after %d)", (long long)i, (int)rp[i + 1], (int)rp[i]);
+      throw hymls::Error(-2, buf);
+    }
+  // (rowptr is int32 and does not decrease, so nnz < 2^31: a larger matrix cannot be expressed and shows as a decrease)
+  const int64_t nnz = rp[n];
+  HYMLS_CHECK(nnz == 0 || (colind && values), -2, "set_mass_matrix: null colind or values");
+  const int32_t* col = colind;
+  if (on_device && nnz > 0) { hcol.resize(nnz); dev::d2h(hcol.data(), colind, (size_t)nnz * sizeof(int32_t)); col = hcol.data(); }
+  for (int64_t k = 0; k < nnz; k++)
+    if (col[k] < 0 || col[k] >= n) {
+      char buf[128];
+      std::snprintf(buf, sizeof buf, "set_mass_matrix: column %d at entry %lld lies outside [0, %lld)", (int)col[k], (long long)k, (long long)n);
+      throw hymls::Error(-2, buf);
+    }
+  const size_t bytes = (size_t)nnz * (sizeof(double) + sizeof(int32_t)) + (size_t)(n + 1) * sizeof(int32_t);
+  try {
+    s->b_buf = dev::alloc(bytes);
+  } catch (...) {
+    char buf[192];
+    std::snprintf(buf, sizeof buf, "set_mass_matrix: could not allocate %zu bytes of device memory for the mass matrix (the solver "
+                  "is left without one)", bytes);
+    throw hymls::Error(-3, buf);
+  }
+  double* dval = (double*)s->b_buf;
+  int32_t* drp = (int32_t*)(dval + nnz);
+  int32_t* dcol = drp + (n + 1);
+  try {
+    if (on_device) {
+      dev::d2d(drp, rowptr, (size_t)(n + 1) * sizeof(int32_t));
+      if (nnz > 0) { dev::d2d(dcol, colind, (size_t)nnz * sizeof(int32_t)); dev::d2d(dval, values, (size_t)nnz * sizeof(double)); }
+    } else {
+      dev::h2d(drp, rowptr, (size_t)(n + 1) * sizeof(int32_t));
+      if (nnz > 0) { dev::h2d(dcol, colind, (size_t)nnz * sizeof(int32_t)); dev::h2d(dval, values, (size_t)nnz * sizeof(double)); }
+    }
+    dev::sync();
+  } catch (...) {
+    free_mass(s);
+    throw;
+  }
+  s->b_rp = drp; s->b_col = dcol; s->b_val = dval;
+  s->b_n = n; s->b_nnz = nnz;
+#endif
+  SOLVER_END
+  return 0;
+}
+
+int hymls_mi_solver_apply_mass(hymls_mi_solver_t* s, const double* X, int64_t ldx, double* Y, int64_t ldy, int nvec, int on_device) {
+  if (!s) return -2;
+  SOLVER_BEGIN
+#ifndef HYMLS_MI_SHIFTED_SOLVER
+  (void)X; (void)ldx; (void)Y; (void)ldy; (void)nvec; (void)on_device;
+  SHIFT_MISSING;
+#else
+  HYMLS_CHECK(hv_.top, -1, "apply_mass needs an initialized handle (its row count)");
+  const int64_t n = hv_.top->num_owned();
+  HYMLS_CHECK(nvec >= 0 && (nvec == 0 || (X && Y && ldx >= n && ldy >= n)), -2, "apply_mass: need non-null X, Y and ldx, ldy >= n");
+  if (nvec == 0) return 0;
+  HYMLS_CHECK(!s->b_buf || s->b_n == n, -2, "the mass matrix does not have the row count of the handle");
+  if (on_device) {
+    HYMLS_CHECK(!columns_overlap(X, ldx, Y, ldy, n, nvec), -2, "apply_mass: X and Y overlap");
+    dev::kry_shifted_product((int32_t)n, nullptr, nullptr, nullptr, -1, s->b_rp, s->b_col, s->b_val, 0.0, 1.0, X, ldx, Y, ldy, nvec);
+    dev::sync();
+  } else {
+    Scratch stage((size_t)2 * nvec * n);
+    double* buf = stage.p;
+    for (int v = 0; v < nvec; v++) dev::h2d(buf + (int64_t)v * n, X + (int64_t)v * ldx, n * sizeof(double));
+    dev::kry_shifted_product((int32_t)n, nullptr, nullptr, nullptr, -1, s->b_rp, s->b_col, s->b_val, 0.0, 1.0, buf, n,
+                             buf + (int64_t)nvec * n, n, nvec);
+    for (int v = 0; v < nvec; v++) dev::d2h(Y + (int64_t)v * ldy, buf + (int64_t)(nvec + v) * n, n * sizeof(double));
+  }
+#endif
+  SOLVER_END
+  return 0;
+}
+
+int hymls_mi_solver_set_shift(hymls_mi_solver_t* s, double shift_a, double shift_b) {
+  if (!s) return -2;
+  try {
+#ifndef HYMLS_MI_SHIFTED_SOLVER
+    (void)shift_a; (void)shift_b;
+    SHIFT_MISSING;
+#else
+    HYMLS_CHECK(std::isfinite(shift_a) && std::isfinite(shift_b), -2, "set_shift: the shifts must be finite");
+    HYMLS_CHECK(shift_a != 0.0 || shift_b != 0.0, -2, "set_shift: a = b = 0 is the zero operator");
+    s->sh_a = shift_a;
+    s->sh_b = shift_b;
+#endif
+  } catch (const hymls::Error& e) { s->err = e.what(); return e.code; }
+  return 0;
+}
+
+int hymls_mi_solver_shift(const hymls_mi_solver_t* s, double* shift_a, double* shift_b) {
+  if (!s) return -2;
+#ifndef HYMLS_MI_SHIFTED_SOLVER
+  (void)shift_a; (void)shift_b;
+  return -99;
+#else
+  if (shift_a) *shift_a = s->sh_a;
+  if (shift_b) *shift_b = s->sh_b;
+  return 0;
+#endif
+}
+
+int hymls_mi_shifted_product(hymls_mi_t* h, int64_t n, double a, const int32_t* rpA, const int32_t* colA, const double* valA,
+                             int64_t nnzA_hint, double b, const int32_t* rpB, const int32_t* colB, const double* valB,
+                             const double* X, int64_t ldx, double* Y, int64_t ldy, int nvec) {
+  if (!h) return -2;
+  HandleView hv = handle_view(h);
+  try {
+#ifndef HYMLS_MI_SHIFTED_SOLVER
+    (void)n; (void)a; (void)rpA; (void)colA; (void)valA; (void)nnzA_hint; (void)b; (void)rpB; (void)colB; (void)valB;
+    (void)X; (void)ldx; (void)Y; (void)ldy; (void)nvec;
+    SHIFT_MISSING;
+#else
+    dev::bind(hv.ctx);
+    HYMLS_CHECK(n >= 1 && n < ((int64_t)1 << 31) && nvec >= 0, -2, "shifted_product: need 1 <= n < 2^31 and nvec >= 0");
+    if (nvec == 0) return 0;
+    HYMLS_CHECK(X && Y && ldx >= n && ldy >= n, -2, "shifted_product: need non-null X, Y and ldx, ldy >= n");
+    HYMLS_CHECK(a == 0.0 || (rpA && colA && valA), -2, "shifted_product: null arrays of A with a != 0");
+    HYMLS_CHECK(!rpB || (colB && valB), -2, "shifted_product: B has a rowptr, but null colind or values");
+    HYMLS_CHECK(!columns_overlap(X, ldx, Y, ldy, n, nvec), -2, "shifted_product: X and Y overlap");
+    dev::kry_shifted_product((int32_t)n, rpA, colA, valA, nnzA_hint, rpB, colB, valB, a, b, X, ldx, Y, ldy, nvec);
     dev::sync();
 #endif
   } catch (const hymls::Error& e) { *hv.err = e.what(); return e.code; }
@@ -1410,6 +1630,7 @@ void hymls_mi_solver_destroy(hymls_mi_solver_t* s) {
     dev::sync();
     free_buffers(s);
     free_projection(s);
+    free_mass(s);
     dev::kry_timer_destroy(s->timer);
   } catch (...) {}
   delete s;

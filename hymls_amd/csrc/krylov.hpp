@@ -171,6 +171,21 @@ void kry_proj_update(int64_t n, int32_t m, const double* P, int64_t ldp, const d
 void kry_oblique_project(int64_t n, int32_t m, const double* Q, int64_t ldq, const double* dG, const double* P, int64_t ldp,
                          const double* x, double* y, const KryWork& ws);
 
+// ---- shifted operator (hymls_mi_solver_set_shift, hymls_mi_solver_set_mass_matrix; the reference's HYMLS::ShiftedOperator):
+//   Y(:, v) = a * A X(:, v) + b * B X(:, v),  v < nv;  B (rpB) == nullptr: the identity
+// A, B: CSR with 32-bit indices and n rows on the device, X, Y column-major with leading dimensions ldx, ldy >= n; X and Y
+// must not overlap.  One kernel reads both matrices and writes Y once.  L = spmv_lanes(n, nnzA_hint) consecutive lanes share
+// a row and form two partial sums, sA over the row of A and sB over the row of B, each exactly as k_spmv<L> forms its sum
+// (entries rp[row] + lane, step L, ascending, then the __shfl_down tree); lane 0 writes a * sA + b * sB.  Without B, sB is
+// x[row]; with b == 0 B is not read and lane 0 writes a * sA; with a == 0 A is not read (its arrays may be null) and lane 0
+// writes b * sB.  The columns go in groups of up to four (a lane loads each entry once and keeps the sums of every column of
+// the group), and column v has the bits of the nv = 1 call on that column.  The grid is that of spmv() for n and L.  No
+// atomics.  Implemented by krylov_hip.hip and by the test-only tests/krylov_shift_sim; krylov.cpp refers to it only under
+// HYMLS_MI_SHIFTED_SOLVER, because the other simulators have none.
+void kry_shifted_product(int32_t n, const int32_t* rpA, const int32_t* colA, const double* valA, int64_t nnzA_hint,
+                         const int32_t* rpB, const int32_t* colB, const double* valB, double a, double b, const double* X,
+                         int64_t ldx, double* Y, int64_t ldy, int nv);
+
 // phase timing of a solve: events recorded on the stream (the simulator takes host clock readings)
 struct KryTimer;
 KryTimer* kry_timer_create();

@@ -13,6 +13,7 @@
 //                       tree, on the device, so h1 feeds pass B and h2 pass C without a host round trip
 //   k_kry_border_*      the border product of a bordered system [K V; W' C] behind K x: y += V s and the tail W' x + C s
 //   k_kry_proj_*        projection vectors: y = x - P (G (Q' x)), the coefficients in two stages and one update pass
+//   k_kry_shifted       the shifted operator y = a K x + b B x: both CSR matrices in one pass, y written once
 // plus the vector passes of GMRES and CG.  No atomics anywhere: every result is bitwise reproducible.
 //
 // Every pass is written once, as a __device__ body (kry_*_body, kry_column_sum); a __global__ kernel only finds its operands
@@ -375,6 +376,64 @@ __global__ void __launch_bounds__(256) k_kry_proj_update(int64_t n, int m, const
   }
 }
 
+// ---- shifted operator (krylov.hpp: kry_shifted_product): Y(:, v) = a A X(:, v) + b B X(:, v) for NV columns in one pass.
+// The L lanes of a row keep two sums per column, over the row of A and over the row of B, each formed as k_spmv<L>
+// (device_hip.hip) forms its sum: entries rp[row] + lane, step L, ascending, then the __shfl_down tree.  A lane loads each
+// (col, val) pair once for all NV columns.  a == 0, b == 0 and rpB == nullptr are uniform over the launch, so every lane of
+// a sub-wave takes the same branches and takes part in the shuffles; the trip count of the grid-stride loop is uniform inside
+// a workgroup for the same reason as in k_spmv.  One body for every L and NV: the single-vector form is NV = 1.
+template <int L, int NV>
+__global__ void __launch_bounds__(256) k_kry_shifted(int32_t n, const int32_t* __restrict__ rpA, const int32_t* __restrict__ colA,
+                                                     const double* __restrict__ valA, const int32_t* __restrict__ rpB,
+                                                     const int32_t* __restrict__ colB, const double* __restrict__ valB, double a,
+                                                     double b, const double* __restrict__ x, int64_t ldx, double* __restrict__ y,
+                                                     int64_t ldy) {
+  const int lane = (int)(threadIdx.x % L);
+  const int rpb = (int)blockDim.x / L;   // rows per block and pass
+  const bool useA = a != 0.0, useB = b != 0.0, haveB = rpB != nullptr;
+  for (int64_t base = (int64_t)blockIdx.x * rpb; base < n; base += (int64_t)gridDim.x * rpb) {
+    const int64_t row = base + threadIdx.x / L;
+    double sA[NV], sB[NV];
+#pragma unroll
+    for (int v = 0; v < NV; v++) sA[v] = sB[v] = 0.0;
+    if (row < n) {
+      if (useA) {
+        const int e = rpA[row + 1];
+        for (int k = rpA[row] + lane; k < e; k += L) {
+          const double av = valA[k];
+          const int64_t c = colA[k];
+#pragma unroll
+          for (int v = 0; v < NV; v++) sA[v] += av * x[c + v * ldx];
+        }
+      }
+      if (useB && haveB) {
+        const int e = rpB[row + 1];
+        for (int k = rpB[row] + lane; k < e; k += L) {
+          const double bv = valB[k];
+          const int64_t c = colB[k];
+#pragma unroll
+          for (int v = 0; v < NV; v++) sB[v] += bv * x[c + v * ldx];
+        }
+      } else if (useB && lane == 0) {   // the identity: the row sum is x[row] itself
+#pragma unroll
+        for (int v = 0; v < NV; v++) sB[v] = x[row + v * ldx];
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+      if (useA) {
+#pragma unroll
+        for (int off = L / 2; off > 0; off >>= 1) sA[v] += __shfl_down(sA[v], off, L);
+      }
+      if (useB && haveB) {
+#pragma unroll
+        for (int off = L / 2; off > 0; off >>= 1) sB[v] += __shfl_down(sB[v], off, L);
+      }
+      if (row < n && lane == 0) y[row + v * ldy] = !useB ? a * sA[v] : (!useA ? b * sB[v] : a * sA[v] + b * sB[v]);
+    }
+  }
+}
+
 // ---- lock-step columns (krylov.hpp: KryBatch, KryVecBatch): blockIdx.y is the column.  Each kernel calls the body of its
 // single-column kernel above with the operands of its column and the column's own grid: a column strides by the grid its
 // single-column launch would have had and writes that many partials, so its sums are added in the same order and give the
@@ -613,6 +672,38 @@ void kry_oblique_project(int64_t n, int32_t m, const double* Q, int64_t ldq, con
   if (ldp < n) throw Error(-2, "oblique projection: n >= 1, 1 <= m <= 32, ldp >= n");   // before the first launch
   kry_proj_coeffs(n, m, Q, ldq, dG, x, ws);
   kry_proj_update(n, m, P, ldp, x, y, ws);
+}
+
+template <int L>
+static void shifted_launch(int nv, dim3 grid, int32_t n, const int32_t* rpA, const int32_t* colA, const double* valA, const int32_t* rpB,
+                           const int32_t* colB, const double* valB, double a, double b, const double* x, int64_t ldx, double* y,
+                           int64_t ldy) {
+  switch (nv) {
+    case 1: hipLaunchKernelGGL((k_kry_shifted<L, 1>), grid, dim3(256), 0, kstream(), n, rpA, colA, valA, rpB, colB, valB, a, b, x, ldx, y, ldy); break;
+    case 2: hipLaunchKernelGGL((k_kry_shifted<L, 2>), grid, dim3(256), 0, kstream(), n, rpA, colA, valA, rpB, colB, valB, a, b, x, ldx, y, ldy); break;
+    case 3: hipLaunchKernelGGL((k_kry_shifted<L, 3>), grid, dim3(256), 0, kstream(), n, rpA, colA, valA, rpB, colB, valB, a, b, x, ldx, y, ldy); break;
+    default: hipLaunchKernelGGL((k_kry_shifted<L, 4>), grid, dim3(256), 0, kstream(), n, rpA, colA, valA, rpB, colB, valB, a, b, x, ldx, y, ldy); break;
+  }
+  kcheck();
+}
+void kry_shifted_product(int32_t n, const int32_t* rpA, const int32_t* colA, const double* valA, int64_t nnzA_hint,
+                         const int32_t* rpB, const int32_t* colB, const double* valB, double a, double b, const double* X,
+                         int64_t ldx, double* Y, int64_t ldy, int nv) {
+  if (n < 1 || nv < 0 || ldx < n || ldy < n || !X || !Y || (a != 0.0 && (!rpA || !colA || !valA)) || (rpB && (!colB || !valB)))
+    throw Error(-2, "shifted product: n >= 1, nv >= 0, ldx, ldy >= n, non-null X, Y and arrays of A (unless a = 0)");
+  const int L = spmv_lanes(n, nnzA_hint);
+  const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(((int64_t)n * L + 255) / 256, 1 << 20)));   // the grid of spmv()
+  for (int v0 = 0; v0 < nv; v0 += 4) {
+    const int g = std::min(4, nv - v0);
+    const double* xg = X + (int64_t)v0 * ldx;
+    double* yg = Y + (int64_t)v0 * ldy;
+    switch (L) {
+      case 1: shifted_launch<1>(g, grid, n, rpA, colA, valA, rpB, colB, valB, a, b, xg, ldx, yg, ldy); break;
+      case 2: shifted_launch<2>(g, grid, n, rpA, colA, valA, rpB, colB, valB, a, b, xg, ldx, yg, ldy); break;
+      case 4: shifted_launch<4>(g, grid, n, rpA, colA, valA, rpB, colB, valB, a, b, xg, ldx, yg, ldy); break;
+      default: shifted_launch<8>(g, grid, n, rpA, colA, valA, rpB, colB, valB, a, b, xg, ldx, yg, ldy); break;
+    }
+  }
 }
 
 // ---- lock-step launchers

@@ -262,6 +262,12 @@ class LevelSolver : public Operator {
   // bits of matvec.  One GPU only: a sharded handle throws -99
   void matvec_mv(const double* x, int64_t ldx, double* y, int64_t ldy, int nv);
 #endif
+#ifdef HYMLS_MI_SHIFTED_SOLVER
+  // the device CSR arrays of K that matvec hands to dev::spmv (read-only, for the shifted operator a K + b B of the native
+  // Krylov solver), its row count and its nnz.  One GPU.  Fetch them at every product: a SetMatrix with a new pattern moves them
+  struct DeviceCsr { int32_t n; const int32_t* rowptr; const int32_t* col; const double* val; int64_t nnz; };
+  DeviceCsr k_device() const { return {K_.n, d_krow_, d_kcol_, d_kval_, K_.nnz()}; }
+#endif
 
   // introspection
   const HierMap& hiermap() const { return hm_; }

@@ -12,6 +12,9 @@ of their own when the first NativeBorderedSolver or ``border_product`` is used.
 
 ``NativeSolver.setProjectionVectors(V, W)`` is the reference's ``BaseSolver::setProjectionVectors``: the solve then runs in
 the complement of a small space (hymls_mi_solver_set_projection).  Its symbols are bound from a third table.
+
+``NativeSolver.SetMassMatrix(B)``, ``ApplyMass(X)`` and ``setShift(a, b)`` are the reference's methods of those names: with a
+shift the solve is with a K + b B (hymls_mi_solver_set_shift, the reference's ``HYMLS::ShiftedOperator``).  A fourth table.
 """
 import ctypes as C
 
@@ -87,6 +90,29 @@ _SIG_PROJECTION = {
 }
 MAX_PROJECTION = 32
 PROJECTION_FORMS = {"folded": 0, "literal": 1}    # "MI Projection Form" (hymls_mi_solver_set_projection_form)
+
+
+# bound apart from _SIG as well (bind_shifted): mass matrix, shift and the shifted product
+_SIG_SHIFTED = {
+    "hymls_mi_solver_set_mass_matrix": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "hymls_mi_solver_apply_mass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int]),
+    "hymls_mi_solver_set_shift": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "hymls_mi_solver_shift": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "hymls_mi_shifted_product": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                           C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                           C.c_int64, C.c_int]),
+}
+
+
+def bind_shifted(lib):
+    """declare the mass matrix and shift symbols on a loaded library (once); AttributeError if it lacks one"""
+    if not getattr(lib, "_hymls_shifted_bound", False):
+        for name, (res, args) in _SIG_SHIFTED.items():
+            f = getattr(lib, name)
+            f.restype = res
+            f.argtypes = args
+        lib._hymls_shifted_bound = True
+    return lib
 
 
 def bind_projection(lib):
@@ -265,6 +291,53 @@ class NativeSolver:
         self._check(lib.hymls_mi_solver_apply_projected(self._s, which, Xc.ctypes.data, Y.ctypes.data, 0))
         return Y
 
+    def SetMassMatrix(self, B):
+        """the mass matrix B of the shifted operator a K + b B (the reference's SetMassMatrix; hymls_mi_solver_set_mass_matrix):
+        a scipy sparse matrix of the size of K, converted to CSR with 32-bit indices as it is stored (duplicates add up);
+        the solver keeps a device copy.  B=None removes it, and the identity is used."""
+        lib = bind_shifted(self._lib)
+        if B is None:
+            self._check(lib.hymls_mi_solver_set_mass_matrix(self._s, self._P._n, None, None, None, 0))
+            return
+        Bc = B.tocsr()
+        if Bc.shape[0] != Bc.shape[1]:
+            raise ValueError("the mass matrix must be square")
+        if Bc.nnz >= 2 ** 31:
+            raise ValueError("the mass matrix has 2^31 or more entries")
+        rp = np.ascontiguousarray(Bc.indptr, dtype=np.int32)
+        ci = np.ascontiguousarray(Bc.indices, dtype=np.int32)
+        va = np.ascontiguousarray(Bc.data, dtype=np.float64)
+        self._check(lib.hymls_mi_solver_set_mass_matrix(self._s, Bc.shape[0], rp.ctypes.data, ci.ctypes.data, va.ctypes.data, 0))
+
+    def ApplyMass(self, X):
+        """B X (the reference's ApplyMass; X itself without a mass matrix).  X: torch tensor on the device, (n,) or (nvec, n),
+        or numpy array in host memory, (n,) or (n, nvec), as in ApplyInverse"""
+        lib = bind_shifted(self._lib)
+        n = self._P._n
+        if hasattr(X, "data_ptr"):
+            Xc = X.contiguous()
+            assert Xc.shape[-1] == n
+            Y = Xc.new_empty(Xc.shape)
+            nvec = 1 if Xc.dim() == 1 else Xc.shape[0]
+            self._check(lib.hymls_mi_solver_apply_mass(self._s, Xc.data_ptr(), n, Y.data_ptr(), n, nvec, 1))
+            return Y
+        Xc = np.asfortranarray(np.asarray(X, dtype=np.float64))
+        assert Xc.shape[0] == n
+        Y = np.empty_like(Xc, order="F")
+        nvec = 1 if Xc.ndim == 1 else Xc.shape[1]
+        self._check(lib.hymls_mi_solver_apply_mass(self._s, Xc.ctypes.data, n, Y.ctypes.data, n, nvec, 0))
+        return Y
+
+    def setShift(self, a, b):
+        """the solve is with a K + b B instead of K (the reference's setShift; B: SetMassMatrix, else the identity); the
+        preconditioner stays that of K.  (1, 0), the default, is the plain solve"""
+        self._check(bind_shifted(self._lib).hymls_mi_solver_set_shift(self._s, float(a), float(b)))
+
+    def getShift(self):
+        a, b = C.c_double(), C.c_double()
+        self._check(bind_shifted(self._lib).hymls_mi_solver_shift(self._s, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def SetTolerance(self, tol):
         self._check(self._lib.hymls_mi_solver_set_tolerance(self._s, float(tol)))
 
@@ -402,6 +475,19 @@ def border_product(P, n, m, V, ldv, W, ldw, C_, z, y):
     ptr = lambda a: a.data_ptr() if a is not None else None
     ierr = lib.hymls_mi_border_product(P._h, n, m, ptr(V), ldv, ptr(W), ldw, Cm.ctypes.data if Cm is not None else None,
                                        ptr(z), ptr(y))
+    if ierr:
+        raise HymlsError(ierr, lib.hymls_mi_last_error(P._h).decode())
+
+
+def shifted_product(P, n, a, A, b, B, X, ldx, Y, ldy, nvec, nnz_hint=-1):
+    """Y(:, v) = a A X(:, v) + b B X(:, v), v < nvec (hymls_mi_shifted_product) on device arrays.  A, B: (rowptr, colind, values)
+    triples of torch tensors (int32, int32, float64; device memory, host memory with the test-only simulator) or None (A: only
+    with a = 0; B: the identity); X, Y: torch tensors, column-major with leading dimensions ldx, ldy, not overlapping.
+    nnz_hint: the nnz of A, from which the lanes per row follow (-1: 4 lanes)."""
+    lib = bind_shifted(P._lib)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    pa, pb = [ptr(t) for t in (A or (None,) * 3)], [ptr(t) for t in (B or (None,) * 3)]
+    ierr = lib.hymls_mi_shifted_product(P._h, n, a, pa[0], pa[1], pa[2], nnz_hint, b, pb[0], pb[1], pb[2], ptr(X), ldx, ptr(Y), ldy, nvec)
     if ierr:
         raise HymlsError(ierr, lib.hymls_mi_last_error(P._h).decode())
 

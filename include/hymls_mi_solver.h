@@ -150,13 +150,57 @@ int hymls_mi_solver_num_projection(const hymls_mi_solver_t* s);
 int hymls_mi_solver_set_projection_form(hymls_mi_solver_t* s, int form);
 /* one vector through the projected operator (which = 0) or the projected preconditioner (which = 1) exactly as the solve
  * applies them (building block, for tests).  X, Y: n entries, device or host as on_device says; Y may be X.  Forms Z and H
- * if the next solve would.  -2 when no projection is set, -1 before Compute. */
+ * if the next solve would.  -2 when no projection is set, -1 before Compute.  With a shift set (below), which = 0 applies the
+ * shifted projected operator, as the solve does. */
 int hymls_mi_solver_apply_projected(hymls_mi_solver_t* s, int which, const double* X, double* Y, int on_device);
 /* building block (as hymls_mi_border_product): y = x - P (G (Q' x)).  P, Q: n x m column-major device arrays, x, y device
  * (y may be x); G host, m x m column-major, may be NULL (the identity).  n >= 1, 1 <= m <= HYMLS_MI_SOLVER_MAX_PROJECTION,
  * ldq, ldp >= n; otherwise -2.  Sums in a fixed order without atomics: the result is bitwise repeatable. */
 int hymls_mi_oblique_project(hymls_mi_t* h, int64_t n, int32_t m, const double* Q, int64_t ldq, const double* G,
                              const double* P, int64_t ldp, const double* x, double* y);
+
+/* Mass matrix and shifted operator (the reference's HYMLS::BaseSolver::SetMassMatrix / ApplyMass / setShift with
+ * HYMLS::ShiftedOperator): with a shift (a, b) other than the default (1, 0), hymls_mi_solver_solve and
+ * hymls_mi_solver_solve_bordered solve with
+ *   operator         y = a K x + b B x,   B the mass matrix, or the identity when none is set
+ * in the place of K x: in the plain operator, inside the projected one, (I - BV V') (a K + b B) (I - V BV'), on the rows of K
+ * of the bordered one, in every explicit residual, in CG and in the product of a lock-step group (K and B are read once per
+ * group of up to four columns).  This is the system of the Jacobi-Davidson correction equation (setShift(1, -sigma), then
+ * set_projection) and of time steppers, (K + sigma B) x = b.  The preconditioner stays ApplyInverse of the handle, the
+ * preconditioner of K alone, and so do Z and H of a projection; convergence stays relative to the first residual, and basis
+ * storage, left and right preconditioning, restarts, start vectors and per-column results work as without a shift.  The
+ * product is one HIP kernel that reads both matrices and writes y once, without atomics (bitwise repeatable), and counts as
+ * K x (phase 2) in the phase timing; its row sums of K use the lanes of hymls_mi_matvec.
+ * B and the shift are state like the projection vectors: hymls_mi_solver_set_params does not touch them.  With (1, 0) the
+ * solver takes the path and gives the bits of one that never had a shift, whether or not a mass matrix is set.  One GPU: a
+ * solve with another shift on a sharded handle returns -99; the plain sharded solve is untouched.
+ *
+ * hymls_mi_solver_set_mass_matrix: B in CSR with n rows and columns, 32-bit rowptr (n + 1 entries) and colind, double values;
+ * device pointers if on_device, else host memory; the solver keeps a device copy of its own, 4 (n + 1) + 12 nnz bytes.  The
+ * entries of a row are summed in storage order, and duplicates add up.  rowptr NULL removes B (the identity is used).  The
+ * entry validates on the host before any kernel reads an index (device input: rowptr and colind are copied back once): -2
+ * with a message when n differs from the handle's row count, rowptr[0] != 0, a rowptr entry decreases (which is also how
+ * nnz >= 2^31 shows in 32-bit row pointers), a column lies outside [0, n), or colind or values is NULL with nnz > 0.  A
+ * failed allocation returns -3 with the bytes asked for in the message.  After any failure the solver has no mass matrix.
+ * hymls_mi_solver_apply_mass: Y(:, v) = B X(:, v), v < nvec (column-major, ldx, ldy >= n); Y = X without a mass matrix.
+ * nvec = 0: nothing; -2: nvec < 0, a leading dimension below n, null arrays, or device X and Y that overlap.
+ * hymls_mi_solver_set_shift: -2 for non-finite values or a = b = 0.  hymls_mi_solver_shift: the pair (either pointer may be
+ * null).
+ * A library built without the shifted product kernel (a test-only simulator) returns -99 from all five entries below. */
+int hymls_mi_solver_set_mass_matrix(hymls_mi_solver_t* s, int64_t n, const int32_t* rowptr, const int32_t* colind,
+                                    const double* values, int on_device);
+int hymls_mi_solver_apply_mass(hymls_mi_solver_t* s, const double* X, int64_t ldx, double* Y, int64_t ldy, int nvec, int on_device);
+int hymls_mi_solver_set_shift(hymls_mi_solver_t* s, double shift_a, double shift_b);
+int hymls_mi_solver_shift(const hymls_mi_solver_t* s, double* shift_a, double* shift_b);
+/* building block (as hymls_mi_border_product), device pointers: Y(:, v) = a A X(:, v) + b B X(:, v), v < nvec, A and B CSR with
+ * n rows, 32-bit indices and double values; rpB NULL: B is the identity.  The caller vouches for the indices of A and B.
+ * Lanes per row from nnzA_hint / n (-1: 4 lanes, those of hymls_mi_matvec); b = 0: B is not read; a = 0: A is not read and
+ * its arrays may be NULL.  Column v has the bits of the nvec = 1 call on it.  nvec = 0: nothing.  -2: n < 1 or n >= 2^31,
+ * nvec < 0, a leading dimension below n, NULL X or Y, NULL arrays of A with a != 0, NULL colB or valB with rpB set, X and Y
+ * overlapping. */
+int hymls_mi_shifted_product(hymls_mi_t* h, int64_t n, double a, const int32_t* rpA, const int32_t* colA, const double* valA,
+                             int64_t nnzA_hint, double b, const int32_t* rpB, const int32_t* colB, const double* valB,
+                             const double* X, int64_t ldx, double* Y, int64_t ldy, int nvec);
 
 /* phase timing with events on the stream (adds a synchronisation at the end of every solve while on).
  * which: 0 whole solve, 1 ApplyInverse, 2 K x, 3 orthogonalisation + updates; seconds summed since profiling was
